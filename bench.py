@@ -31,10 +31,26 @@ GPU, so it defaults to weak scaling with the 8-GPU job's per-GPU share:
   5  logistic n = 5e6, p = 500, K = 32              (wide path: row + Gram pass)
   4  OLS      n = 1.25e8, p = 64, K = 128 per GPU   (1e9 rows / 1024 partitions on 8 GPUs)
 
-Rank 0 prints one JSON line (metric/value/... plus "roofline" for the dominant
-kernel, "parity_rel" of two sampled partitions against the CPU oracle after
-the timed region, and, at N = 1, "cpu_baseline": the numpy oracle on a
-bounded sample of the same workload on host cores, timed by wall clock).
+Rank 0 prints one JSON line: metric/value/ms_per_step/... plus "roofline" and
+"kernels" from the HIP events the timed steps record themselves.  A plain run
+does nothing else: set-up, warm-up, the timed steps, the line.
+
+``--full`` adds what takes runs of its own, all after the timed region: two
+untimed steps with an fp64-MFMA Sig_inv, "parity_rel" of sampled partitions
+against the CPU oracle, "sig_inv_all_partitions" (every partition against an
+independent fp64 library-GEMM evaluation) and, at N = 1, "cpu_baseline": the
+numpy oracle on a bounded sample of the same workload on host cores, timed by
+wall clock.  ``--no-fp64-step``, ``--no-parity`` and ``--no-cpu-baseline``
+drop single legs of a ``--full`` run.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller
+as DIR/<name>.npy (float64; rank 0's shard when N > 1): the per-partition fit
+(theta, sig_inv, sig_inv_theta, loglik, iters, status), the combined sums
+(sig_inv_sum, sig_inv_theta_sum), the WLSE (wlse) and the DBIC-selected LARS
+coefficients (beta_dbic).  At most 64 MB in all: an array that does not fit
+is cut to a fixed, seeded sample of its partitions, whose indices are written
+beside it as <name>_partitions.npy.  The inputs depend only on the arguments
+(--seed), so two builds can be compared output for output.
 """
 
 from __future__ import annotations
@@ -195,6 +211,57 @@ def sampled_parity(fit, X, y, offsets, family, codes=None, levels=None, fit_inte
     return worst, sample
 
 
+# ---------------------------------------------------------------------------
+# --dump-outputs: the last timed step's outputs as .npy files
+# ---------------------------------------------------------------------------
+
+DUMP_MAX_BYTES = 60_000_000  # array bytes; the .npy headers stay well inside the 64 MB limit
+
+
+def sample_partitions(K, row_bytes, budget, seed):
+    """Partitions of a [K, ...] array (row_bytes each) that fit `budget`
+    bytes: all of them (None), else a sorted sample without replacement that
+    depends only on (K, seed) and the count -- at least one partition."""
+    import numpy as np
+
+    m = max(1, int(budget // max(1, row_bytes)))
+    if m >= K:
+        return None
+    return np.sort(np.random.RandomState(seed).permutation(K)[:m])
+
+
+def dump_outputs(out_dir, fit, combined, seed, max_bytes=DUMP_MAX_BYTES):
+    """Write the step's outputs as out_dir/<name>.npy in float64: the fit's
+    per-partition device arrays and the host arrays of `combined`.  Arrays are
+    written smallest first; one that would take the total past `max_bytes` is
+    cut to sample_partitions() of its leading axis, whose indices go to
+    <name>_partitions.npy.  Returns {name: shape written}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = dict(combined)
+    for name in ("theta", "sig_inv", "sig_inv_theta", "loglik", "iters", "status"):
+        arrays[name] = getattr(fit, name)
+    nbytes = lambda a: 8 * int(np.prod(a.shape))  # noqa: E731  (as float64)
+    left = max_bytes
+    written = {}
+    for name in sorted(arrays, key=lambda k: (nbytes(arrays[k]), k)):
+        a = arrays[name]
+        if nbytes(a) > left:
+            K = int(a.shape[0])
+            idx = sample_partitions(K, nbytes(a) // K, left - 8 * K, seed)
+            if idx is not None:
+                a = a[idx.tolist()]
+                np.save(os.path.join(out_dir, name + "_partitions.npy"), idx.astype(np.float64))
+                left -= 8 * len(idx)
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = a.shape
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -217,15 +284,25 @@ def main():
     ap.add_argument("--tol", type=float, default=1e-10)
     ap.add_argument("--cpu-parts", type=int, default=0,
                     help="partitions of the CPU baseline sample (0: ~10-30 s of CPU work per config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the fp64-Sig_inv steps, the parity "
+                         "checks against the oracle and the CPU baseline (off: set-up, warm-up, "
+                         "the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64, at "
+                         "most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: no parity checks")
     ap.add_argument("--no-fp64-step", action="store_true",
-                    help="skip the two untimed fp64-Sig_inv steps reported beside the line")
+                    help="with --full: skip the two untimed fp64-Sig_inv steps reported beside "
+                         "the line")
     ap.add_argument("--seed", type=int, default=2019)
     ap.add_argument("--layout", default="codes", choices=["codes", "dense"],
                     help="config 3: categorical-code layout (LDS-histogram pass) or the dense "
                          "dummy-coded design")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     cfg = dict(CONFIGS[args.config])
@@ -347,7 +424,9 @@ def main():
             stage_ms["fit"] += (t_b - t_a) * 1e3
             stage_ms["reduce_allreduce"] += (t_c - t_b) * 1e3
             stage_ms["wlse_lars_dbic"] += (t_d - t_c) * 1e3
-        return fit, est, support, int(round(Ksum)), int(round(b[-1]))
+        combined = {"sig_inv_sum": S, "sig_inv_theta_sum": v, "wlse": est,
+                    "beta_dbic": lars["beta"][ib]}
+        return fit, combined, support, int(round(Ksum)), int(round(b[-1]))
 
     for _ in range(args.warmup):
         step(False)
@@ -361,7 +440,7 @@ def main():
         # device allocation held the next launches back by ~5 ms
         # (profiles/r05y_c5_host_gaps.txt)
         fit = None
-        fit, est, support, K_red, n_red = step(True)
+        fit, combined, support, K_red, n_red = step(True)
         stats_acc.append(fit.stats)
     torch.cuda.synchronize()
     if use_pg:
@@ -375,12 +454,15 @@ def main():
     assert K_red == K_job and n_red == n_job, (K_red, n_red, K_job, n_job)
     ms_per_step = elapsed / args.steps * 1e3
     value = n_job * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fit, combined, args.seed)
 
     # the same step with an fp64-MFMA Sig_inv, beside the headline line (one
     # step each, after the timed region; N = 1 without a process group only,
     # since a rank-0-only step would wait in the all-reduce)
     fp64_steps = {}
-    if family == "logistic" and not codes_layout and not use_pg and not args.no_fp64_step:
+    if args.full and family == "logistic" and not codes_layout and not use_pg \
+            and not args.no_fp64_step:
         for key, hs, ex in (("sig_inv_fp64_ms_per_step", "fp64", "fp64"),
                             ("exact_fp64_ms_per_step", None, "fp64")):
             torch.cuda.synchronize()
@@ -604,7 +686,7 @@ def main():
             "fp64 MFMA (DLSA_EXACT_FP64) instead of the int8 digit slices")} if fp64_steps else {}),
         "algorithmic": {"bytes_per_pass": n * row_bytes, "flops_per_pass": n * alg_flops_row},
     }
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         # checker, after the timed region: the last step's fit of this rank
         sample = [0] if (wide or data == "dummy") else None  # 1e6-row / P = 500 oracles
         rel, smp = sampled_parity(fit, X, y, offsets, family, codes=codes, levels=levels,
@@ -612,7 +694,7 @@ def main():
         out["parity_rel"] = rel
         out["parity_sample"] = (f"partitions {smp} of rank 0 vs the numpy oracle (tol 1e-12): "
                                 "max |diff| / max |ref| over theta and Sig_inv")
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         # every partition of rank 0 (not a sample): Sig_inv per entry against an
         # independent fp64 library-GEMM evaluation of models.py:114,130 at the
         # returned theta_k, and the WLSE of those independent sums
@@ -633,7 +715,7 @@ def main():
             "H = X_k^T diag(w) X_k at the returned theta_k by torch fp64 GEMMs (an independent "
             "library path); wlse_rel = WLSE of the independent sums vs the product's sums; "
             f"{time.perf_counter() - t_ck:.1f} s, after the timed region")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         workers, cinfo = host_cores()      # every core this process may use
         if args.config == 5:
             nk_cpu, parts = 20000, 16      # ~8 s of single-thread work per partition

@@ -425,6 +425,44 @@ def test_bench_host_cores_reports_quota():
     assert info["affinity"] <= info["nproc"]
 
 
+def test_bench_dump_outputs_samples_within_budget(tmp_path):
+    """bench.py's --dump-outputs writer: every array as float64; an array past
+    the byte budget is cut to a sample of whole partitions that depends only
+    on the seed, its indices written beside it; the total stays in budget."""
+    import importlib.util
+    import types
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert b.DUMP_MAX_BYTES <= 64_000_000
+    K, P = 37, 9
+    rs = np.random.RandomState(0)
+    fit = types.SimpleNamespace(
+        theta=rs.randn(K, P), sig_inv=rs.randn(K, P, P), sig_inv_theta=rs.randn(K, P),
+        loglik=rs.randn(K), iters=np.arange(K, dtype=np.int32), status=np.zeros(K, np.int32))
+    comb = {"sig_inv_sum": fit.sig_inv.sum(0), "wlse": rs.randn(P).astype(np.float32)}
+    budget = 12_000  # sig_inv alone is 37 * 648 = 23 976 bytes
+    dirs = [tmp_path / "a", tmp_path / "b", tmp_path / "c"]
+    for d, seed in zip(dirs, (5, 5, 6)):
+        b.dump_outputs(str(d), fit, comb, seed, max_bytes=budget)
+    got = [{f[:-4]: np.load(d / f) for f in os.listdir(d)} for d in dirs]
+    a = got[0]
+    assert set(a) == {"theta", "sig_inv", "sig_inv_theta", "loglik", "iters", "status",
+                      "sig_inv_sum", "wlse", "sig_inv_partitions"}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= budget
+    idx = a["sig_inv_partitions"].astype(int)
+    assert 1 <= len(idx) < K and len(set(idx)) == len(idx) and (np.diff(idx) > 0).all()
+    assert np.array_equal(a["sig_inv"], fit.sig_inv[idx])
+    for name in ("theta", "sig_inv_theta", "loglik", "iters", "status", "sig_inv_sum"):
+        assert np.array_equal(a[name], np.asarray(getattr(fit, name, comb.get(name)), np.float64))
+    assert all(np.array_equal(a[k], got[1][k]) for k in a)          # same seed: same files
+    assert not np.array_equal(idx, got[2]["sig_inv_partitions"])    # the seed picks the sample
+    assert b.sample_partitions(4, 100, 400, 1) is None              # fits: no sampling
+
+
 # ---- data_info: moments merge and the sharded combine ------------------------
 
 def test_merge_moments_and_describe_frame_match_pandas():

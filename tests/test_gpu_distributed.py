@@ -125,7 +125,7 @@ def test_bench_gpus2_launches_two_ranks(tmp_path):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo",
            "--n", "1600000", "--partitions", "16", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -151,7 +151,7 @@ def test_bench_force_pg_rccl_one_gpu():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--backend", "nccl",
            "--force-pg", "--n", "1600000", "--partitions", "16", "--steps", "2", "--warmup",
-           "1", "--no-cpu-baseline"]
+           "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -24,9 +24,9 @@
 #   unenv:VAR                   unset it again
 #
 # Example (the round's closing run):
-#   TAG=r06z tools/gpu.sh "test:" smoke "bench:c2:" "bench:c3:--config 3 --steps 4 --no-cpu-baseline" \
-#       "prof:c2:--steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-fp64-step" \
-#       "pmc:c2_fetch:FETCH_SIZE:--steps 1 --warmup 0 --no-cpu-baseline --no-parity --no-fp64-step"
+#   TAG=r06z tools/gpu.sh "test:" smoke "bench:c2:--full" \
+#       "bench:c3:--config 3 --steps 4 --full --no-cpu-baseline" \
+#       "prof:c2:--steps 2 --warmup 1" "pmc:c2_fetch:FETCH_SIZE:--steps 1 --warmup 0"
 set -o pipefail
 OUT=gpurun_out/${TAG:?set TAG}; mkdir -p "$OUT"; export TMPDIR=/tmp
 summ() {
