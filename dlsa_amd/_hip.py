@@ -96,6 +96,11 @@ SIGNATURES = {
          _P]),
     "dlsa_logistic_loglik_batched": (
         ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P]),
+    "dlsa_logistic_loglik_batched_sum": (
+        ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
+    "dlsa_logistic_loglik_categorical": (
+        ctypes.c_int,
+        [_P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P]),
     "dlsa_logistic_fit_categorical": (
         ctypes.c_int,
         [_P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _F64, _P, _P, _P, _P, _P, _P,

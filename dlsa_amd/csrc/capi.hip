@@ -1789,11 +1789,10 @@ int dlsa_logistic_fit_batched(const double* X, const double* y, const int64_t* o
                                       iters, status, nullptr, stream);
 }
 
-int dlsa_logistic_loglik_batched(const double* X, const double* y, const int64_t* offsets,
-                                 int32_t K, int32_t p, int32_t fit_intercept,
-                                 const double* center, const double* scale,
-                                 const double* betas, int32_t n_beta, double* loglik,
-                                 void* stream_) {
+static int loglik_dense(const double* X, const double* y, const int64_t* offsets, int32_t K,
+                        int32_t p, int32_t fit_intercept, const double* center,
+                        const double* scale, const double* betas, int32_t n_beta,
+                        double* loglik, double* loglik_sum, void* stream_) {
   g_last_error.clear();
   hipStream_t stream = (hipStream_t)stream_;
   int rc = check_offsets(offsets, K);
@@ -1869,7 +1868,153 @@ int dlsa_logistic_loglik_batched(const double* X, const double* y, const int64_t
     DLSA_HIP_TRY(launch_loglik_eval(ea, pl.n_chunks, stream));
   }
   DLSA_HIP_TRY(launch_loglik_reduce(d_partial, d_pcb, K, n_beta, loglik, stream));
+  if (loglik_sum) DLSA_HIP_TRY(launch_loglik_total(loglik, K, n_beta, loglik_sum, stream));
   DLSA_HIP_TRY(hipStreamSynchronize(stream));
+  return DLSA_OK;
+}
+
+int dlsa_logistic_loglik_batched(const double* X, const double* y, const int64_t* offsets,
+                                 int32_t K, int32_t p, int32_t fit_intercept,
+                                 const double* center, const double* scale,
+                                 const double* betas, int32_t n_beta, double* loglik,
+                                 void* stream) {
+  return loglik_dense(X, y, offsets, K, p, fit_intercept, center, scale, betas, n_beta, loglik,
+                      nullptr, stream);
+}
+
+int dlsa_logistic_loglik_batched_sum(const double* X, const double* y, const int64_t* offsets,
+                                     int32_t K, int32_t p, int32_t fit_intercept,
+                                     const double* center, const double* scale,
+                                     const double* betas, int32_t n_beta, double* loglik,
+                                     double* loglik_sum, void* stream) {
+  return loglik_dense(X, y, offsets, K, p, fit_intercept, center, scale, betas, n_beta, loglik,
+                      loglik_sum, stream);
+}
+
+int dlsa_logistic_loglik_categorical(const double* Xn, const uint8_t* codes, const double* y,
+                                     const int64_t* offsets, int32_t K, int32_t q, int32_t F,
+                                     const int32_t* levels, int32_t fit_intercept,
+                                     const double* center, const double* scale,
+                                     const double* betas, int32_t n_beta, int32_t rows_per_chunk,
+                                     double* loglik, double* loglik_sum, void* stream_) {
+  g_last_error.clear();
+  hipStream_t stream = (hipStream_t)stream_;
+  int rc = check_offsets(offsets, K);
+  if (rc != DLSA_OK) return rc;
+  if (q < 0 || F < 0 || F > kCatMaxFactors || (F > 0 && !levels)) {
+    set_error("need 0 <= q, 0 <= F <= 16 and a host levels[F] array");
+    return DLSA_E_INVALID;
+  }
+  int D = 0;
+  for (int f = 0; f < F; ++f) {
+    if (levels[f] < 1 || levels[f] > 256) {
+      set_error("levels[" + std::to_string(f) + "] must be in 1..256 (uint8 codes)");
+      return DLSA_E_INVALID;
+    }
+    D += levels[f] - 1;
+  }
+  const int ic = fit_intercept ? 1 : 0;
+  const int P = ic + q + D;
+  if (P < 1 || P > DLSA_MAX_P || ic + q > kCatQMax) {
+    set_error("categorical evaluation needs 1 <= P = intercept + q + sum(levels - 1) <= " +
+              std::to_string(DLSA_MAX_P) + " and intercept + q <= " + std::to_string(kCatQMax) +
+              " (got P = " + std::to_string(P) + ")");
+    return DLSA_E_UNSUPPORTED;
+  }
+  if (n_beta < 1 || n_beta > kEvalCatMaxB || rows_per_chunk < 0 || !betas || !loglik ||
+      (center == nullptr) != (scale == nullptr)) {
+    set_error("dlsa_logistic_loglik_categorical: invalid arguments (1 <= n_beta <= 16, "
+              "rows_per_chunk >= 0, center and scale both or neither)");
+    return DLSA_E_INVALID;
+  }
+  const int64_t n_total = offsets[K];
+  if (n_total > 0 && (!y || (q > 0 && !Xn) || (F > 0 && !codes))) {
+    set_error("null Xn, codes or y");
+    return DLSA_E_INVALID;
+  }
+  EvalCatArgs ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.q = q;
+  ea.F = F;
+  ea.P = P;
+  ea.intercept = ic;
+  ea.nbeta = n_beta;
+  for (int f = 0, o = 0; f < F; ++f) {
+    ea.levels[f] = levels[f];
+    ea.toff[f] = o;
+    o += levels[f];
+  }
+  if (!eval_cat_plan(ea)) {
+    set_error("categorical evaluation: the coefficient table does not fit the LDS");
+    return DLSA_E_UNSUPPORTED;
+  }
+  Plan pl;
+  make_plan(offsets, K, q, ic, rows_per_chunk, pl);
+  const int nc = std::max(pl.n_chunks, 1);
+  const int64_t bytes = align_up(8LL * nc, 256) + 2 * align_up(4LL * nc, 256) +
+                        align_up(4LL * (K + 1), 256) + align_up(8LL * nc * n_beta, 256);
+  char* ws = nullptr;
+  DLSA_HIP_TRY(hipMallocAsync((void**)&ws, bytes, stream));
+  struct Free {
+    char* p;
+    hipStream_t s;
+    ~Free() {
+      if (p) (void)hipFreeAsync(p, s);
+    }
+  } freer{ws, stream};
+  int64_t o = 0;
+  int64_t* d_row0 = (int64_t*)(ws + o);
+  o += align_up(8LL * nc, 256);
+  int32_t* d_rows = (int32_t*)(ws + o);
+  o += align_up(4LL * nc, 256);
+  int32_t* d_bad = (int32_t*)(ws + o);
+  o += align_up(4LL * nc, 256);
+  int32_t* d_pcb = (int32_t*)(ws + o);
+  o += align_up(4LL * (K + 1), 256);
+  double* d_partial = (double*)(ws + o);
+  DLSA_HIP_TRY(hipMemcpyAsync(d_pcb, pl.part_chunk_begin.data(), 4LL * (K + 1),
+                              hipMemcpyHostToDevice, stream));
+  std::vector<int32_t> h_bad(pl.n_chunks, 0);
+  if (pl.n_chunks > 0) {
+    DLSA_HIP_TRY(hipMemcpyAsync(d_row0, pl.chunk_row0.data(), 8LL * pl.n_chunks,
+                                hipMemcpyHostToDevice, stream));
+    DLSA_HIP_TRY(hipMemcpyAsync(d_rows, pl.chunk_rows.data(), 4LL * pl.n_chunks,
+                                hipMemcpyHostToDevice, stream));
+    ea.Xn = Xn;
+    ea.codes = codes;
+    ea.y = y;
+    ea.chunk_row0 = d_row0;
+    ea.chunk_rows = d_rows;
+    ea.center = center;
+    ea.scale = scale;
+    ea.betas = betas;
+    ea.partial = d_partial;
+    ea.bad = d_bad;
+    if (q > 0) {
+      ea.x_lo = ((uintptr_t)Xn + 15) & ~(uintptr_t)15;
+      ea.x_hi = (uintptr_t)(Xn + n_total * (int64_t)q) & ~(uintptr_t)15;
+    }
+    if (F > 0) {
+      ea.c_lo = ((uintptr_t)codes + 15) & ~(uintptr_t)15;
+      ea.c_hi = (uintptr_t)(codes + n_total * (int64_t)F) & ~(uintptr_t)15;
+    }
+    ea.y_last4 = (uintptr_t)(y + n_total) - 4;
+    DLSA_HIP_TRY(launch_loglik_cat(ea, pl.n_chunks, stream));
+    DLSA_HIP_TRY(hipMemcpyAsync(h_bad.data(), d_bad, 4LL * pl.n_chunks, hipMemcpyDeviceToHost,
+                                stream));
+  }
+  DLSA_HIP_TRY(launch_loglik_reduce(d_partial, d_pcb, K, n_beta, loglik, stream));
+  if (loglik_sum) DLSA_HIP_TRY(launch_loglik_total(loglik, K, n_beta, loglik_sum, stream));
+  DLSA_HIP_TRY(hipStreamSynchronize(stream));
+  for (int k = 0; k < K; ++k) {
+    int64_t nbad = 0;
+    for (int c = pl.part_chunk_begin[k]; c < pl.part_chunk_begin[k + 1]; ++c) nbad += h_bad[c];
+    if (nbad) {
+      set_error("partition " + std::to_string(k) + ": " + std::to_string(nbad) +
+                " level codes >= levels[f]");
+      return DLSA_E_INVALID;
+    }
+  }
   return DLSA_OK;
 }
 

@@ -300,6 +300,32 @@ struct CatArgs {
   const double* hscale;
 };
 
+// Log-likelihood evaluation pass on the categorical-code layout
+// (eval_cat_pass.hip): P <= DLSA_MAX_P, the other limits are the fit's.
+constexpr int kEvalCatMaxB = 16;
+struct EvalCatArgs {
+  const double* Xn;           // [n_total, q]
+  const uint8_t* codes;       // [n_total, F]
+  const double* y;            // [n_total]
+  const int64_t* chunk_row0;
+  const int32_t* chunk_rows;
+  const double* center;       // [q] or null
+  const double* scale;
+  const double* betas;        // [nbeta, P]
+  double* partial;            // [n_chunks, nbeta]
+  int32_t* bad;               // [n_chunks] codes >= levels[f] met in the chunk
+  // LDS-DMA source windows: the whole 16-byte granules inside Xn / codes
+  // ([lo, hi), both multiples of 16; empty: lo >= hi) and the last 4 bytes of y
+  uintptr_t x_lo, x_hi, c_lo, c_hi, y_last4;
+  int32_t q, F, P, intercept, nbeta;
+  int32_t rb, nslot;          // rows per block, ring depth (eval_cat_plan)
+  int32_t levels[kCatMaxFactors];
+  int32_t toff[kCatMaxFactors];  // first table entry of factor f: sum of levels[0..f)
+};
+bool eval_cat_plan(EvalCatArgs& a);  // sets rb and nslot; false: does not fit the LDS
+hipError_t launch_loglik_cat(const EvalCatArgs& a, int n_chunks, hipStream_t s);
+hipError_t launch_loglik_total(const double* ll, int K, int B, double* out, hipStream_t s);
+
 // Row repartitioning (partition_rows.hip): stable counting sort by partition id.
 constexpr int kPartMaxArrays = 4;
 constexpr int kPartMaxK = 16000;    // LDS histogram / cursors

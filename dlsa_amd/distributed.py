@@ -72,6 +72,43 @@ def combine_and_finish(buf, P, fit_intercept=False, lars_type="lasso", group=Non
     return finish(S, v, st, K, int(round(float(b[-1]))), fit_intercept, lars_type)
 
 
+def reduce_loglik(ll_kb, group=None):
+    """Job-level log-likelihoods from this rank's [K, B] per-partition values
+    (CPU or device tensor, or array-like): the sum over k in fixed order, then
+    ONE ``combine`` of the B doubles.  Returns a numpy [B] array, the same on
+    every rank; without a process group the plain local sum."""
+    import torch
+
+    t = ll_kb if isinstance(ll_kb, torch.Tensor) else torch.from_numpy(
+        np.ascontiguousarray(ll_kb, dtype=np.float64))
+    tot = np.zeros(t.shape[1], dtype=np.float64)
+    for row in t.detach().cpu().numpy():  # K x B doubles: summed on the host, k ascending
+        tot += row
+    # the exchange runs where the values live: RCCL on a device buffer, gloo on a host one
+    return combine(torch.from_numpy(tot).to(t.device), group).cpu().numpy()
+
+
+def loglik_sharded(X, y, offsets, betas, fit_intercept=False, center=None, scale=None,
+                   codes=None, levels=None, group=None):
+    """Second pass of a sharded job (dlsa/model_eval.py:10-42): the
+    log-likelihood of each candidate row of ``betas`` [B, P] over the whole
+    data set.  X, y, offsets describe the LOCAL shard as in
+    ``dlsa_fit_sharded`` (with ``codes``/``levels`` X holds the numeric columns
+    of the categorical-code layout).  The local pass leaves the [B] total of
+    this rank's partitions on the device; ONE all-reduce of those B doubles
+    gives every rank the global sums.  Returns a numpy [B] array."""
+    from .models import logistic_loglik_batched, logistic_loglik_batched_categorical
+
+    if codes is not None:
+        _, tot = logistic_loglik_batched_categorical(
+            X, codes, y, offsets, levels, betas, fit_intercept=fit_intercept, center=center,
+            scale=scale, return_sum=True)
+    else:
+        _, tot = logistic_loglik_batched(X, y, offsets, betas, fit_intercept=fit_intercept,
+                                         center=center, scale=scale, return_sum=True)
+    return combine(tot, group).cpu().numpy()
+
+
 def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
                      group=None, codes=None, levels=None, **fit_kw):
     """Fit this rank's partitions on its GPU and return the global DLSA result.

@@ -360,6 +360,37 @@ def logistic_model_batched(X, y, offsets, fit_intercept=False, center=None, scal
     return BatchedFit(theta, sig, sigt, ll, iters, status, offs, bool(fit_intercept), stats)
 
 
+def _cat_inputs(Xn, codes, y, offsets, levels, center, scale, dev):
+    """Checked device copies of a categorical-code layout: (Xn [n, q] fp64,
+    codes [n, F] uint8, y [n], host offsets [K+1] int64, host levels [F]
+    int32, center, scale ([q] or None))."""
+    Xd = _dev_f64(Xn, dev)
+    if Xd.dim() != 2:
+        raise ValueError("Xn must be 2-D [n, q]")
+    n, q = Xd.shape
+    if isinstance(codes, torch.Tensor):
+        cd8 = codes.to(device=dev, dtype=torch.uint8).contiguous()
+    else:
+        cd8 = torch.from_numpy(np.ascontiguousarray(np.asarray(codes, dtype=np.uint8))).to(dev)
+    if cd8.dim() != 2 or cd8.shape[0] != n:
+        raise ValueError("codes must be [n, F]")
+    lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32).reshape(-1))
+    if lv.size != cd8.shape[1]:
+        raise ValueError("levels must have F entries")
+    yd = _dev_f64(y, dev).reshape(-1)
+    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    K = offs.size - 1
+    if K < 1 or offs[0] != 0 or offs[-1] != n or np.any(np.diff(offs) < 0) or yd.numel() != n:
+        raise ValueError("offsets must be non-decreasing, start at 0 and end at n; y has n rows")
+    cen = sca = None
+    if center is not None or scale is not None:
+        cen = _dev_f64(center, dev).reshape(-1)
+        sca = _dev_f64(scale, dev).reshape(-1)
+        if cen.numel() != q or sca.numel() != q:
+            raise ValueError("center/scale must have q entries (numeric columns)")
+    return Xd, cd8, yd, offs, lv, cen, sca
+
+
 def logistic_model_batched_categorical(Xn, codes, y, offsets, levels, fit_intercept=False,
                                        center=None, scale=None, max_iter=100, tol=1e-10,
                                        record_timing=False, rows_per_chunk=0, zero_partitions=None,
@@ -380,32 +411,10 @@ def logistic_model_batched_categorical(Xn, codes, y, offsets, levels, fit_interc
     ``zero_partitions``: the reference's column-set check fails there too,
     models.py:84-91)."""
     dev = _require_gpu(device)
-    Xd = _dev_f64(Xn, dev)
-    if Xd.dim() != 2:
-        raise ValueError("Xn must be 2-D [n, q]")
-    n, q = Xd.shape
-    if isinstance(codes, torch.Tensor):
-        cd8 = codes.to(device=dev, dtype=torch.uint8).contiguous()
-    else:
-        cd8 = torch.from_numpy(np.ascontiguousarray(np.asarray(codes, dtype=np.uint8))).to(dev)
-    if cd8.dim() != 2 or cd8.shape[0] != n:
-        raise ValueError("codes must be [n, F]")
-    F = cd8.shape[1]
-    lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32).reshape(-1))
-    if lv.size != F:
-        raise ValueError("levels must have F entries")
-    yd = _dev_f64(y, dev).reshape(-1)
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    K = offs.size - 1
-    if K < 1 or offs[0] != 0 or offs[-1] != n or np.any(np.diff(offs) < 0) or yd.numel() != n:
-        raise ValueError("offsets must be non-decreasing, start at 0 and end at n; y has n rows")
+    Xd, cd8, yd, offs, lv, cen, sca = _cat_inputs(Xn, codes, y, offsets, levels, center, scale,
+                                                  dev)
+    q, F, K = Xd.shape[1], cd8.shape[1], offs.size - 1
     P = int(bool(fit_intercept)) + q + int((lv - 1).sum())
-    cen = sca = None
-    if center is not None or scale is not None:
-        cen = _dev_f64(center, dev).reshape(-1)
-        sca = _dev_f64(scale, dev).reshape(-1)
-        if cen.numel() != q or sca.numel() != q:
-            raise ValueError("center/scale must have q entries (numeric columns)")
     theta = torch.empty((K, P), dtype=torch.float64, device=dev)
     sig = torch.empty((K, P, P), dtype=torch.float64, device=dev)
     sigt = torch.empty((K, P), dtype=torch.float64, device=dev)
@@ -472,12 +481,38 @@ def ols_model_batched(X, y, offsets, fit_intercept=False, center=None, scale=Non
                       _hip.last_fit_stats())
 
 
+MAX_LOGLIK_CANDIDATES = 16  # candidates of one evaluation pass (n_beta of the C-ABI)
+
+
+def _loglik_groups(call, betas, P, K, dev, return_sum):
+    """Run ``call(betas_group, g, out [K, g], total [g])`` over the candidates
+    in groups of at most 16 (one pass over the data per group) and assemble
+    the [K, B] log-likelihoods and their [B] sum over k."""
+    bd = _dev_f64(betas, dev)
+    if bd.dim() == 1:
+        bd = bd.reshape(1, -1)
+    if bd.dim() != 2 or bd.shape[0] < 1 or bd.shape[1] != P:
+        raise ValueError("betas must be [B, P] with B >= 1 and P = the design's parameters")
+    B = bd.shape[0]
+    out = torch.empty((K, B), dtype=torch.float64, device=dev)
+    total = torch.empty((B,), dtype=torch.float64, device=dev)
+    for b0 in range(0, B, MAX_LOGLIK_CANDIDATES):
+        g = min(MAX_LOGLIK_CANDIDATES, B - b0)
+        part = out if g == B else torch.empty((K, g), dtype=torch.float64, device=dev)
+        call(bd[b0:b0 + g].contiguous(), g, part, total[b0:b0 + g])
+        if part is not out:
+            out[:, b0:b0 + g] = part
+    return (out, total) if return_sum else out
+
+
 def logistic_loglik_batched(X, y, offsets, betas, fit_intercept=False, center=None, scale=None,
-                            device=None):
+                            device=None, return_sum=False):
     """Per-partition log-likelihood of candidate coefficient vectors in one
     pass over X (the evaluation step of dlsa/models.py:151-225 /
-    dlsa/model_eval.py:10-42).  betas: [B, P] (B <= 16), intercept first.
-    Returns a [K, B] fp64 tensor on the device."""
+    dlsa/model_eval.py:10-42).  betas: [B, P], intercept first; more than 16
+    candidates are evaluated 16 to a pass.  Returns a [K, B] fp64 tensor on
+    the device; with ``return_sum`` also its [B] sum over the partitions (the
+    group-by sum of model_eval.py:38, fixed order, on the device)."""
     dev = _require_gpu(device)
     Xd = _dev_f64(X, dev)
     yd = _dev_f64(y, dev).reshape(-1)
@@ -486,23 +521,48 @@ def logistic_loglik_batched(X, y, offsets, betas, fit_intercept=False, center=No
     K = offs.size - 1
     if K < 1 or offs[0] != 0 or offs[-1] != n or np.any(np.diff(offs) < 0) or yd.numel() != n:
         raise ValueError("offsets must be non-decreasing, start at 0 and end at n; y has n rows")
-    bd = _dev_f64(betas, dev)
-    if bd.dim() == 1:
-        bd = bd.reshape(1, -1)
-    B, P = bd.shape
-    if P != p + (1 if fit_intercept else 0):
-        raise ValueError("betas must have P = p + fit_intercept columns")
     cd = sd = None
     if center is not None or scale is not None:
         cd = _dev_f64(center, dev).reshape(-1)
         sd = _dev_f64(scale, dev).reshape(-1)
-    out = torch.empty((K, B), dtype=torch.float64, device=dev)
     lib = _hip.load()
-    rc = lib.dlsa_logistic_loglik_batched(_ptr(Xd), _ptr(yd), offs.ctypes.data_as(ctypes.c_void_p),
-                                          K, p, int(bool(fit_intercept)), _ptr(cd), _ptr(sd),
-                                          _ptr(bd), B, _ptr(out), _stream(dev))
-    _hip.check(rc, "dlsa_logistic_loglik_batched")
-    return out
+
+    def call(bd, g, out, total):
+        rc = lib.dlsa_logistic_loglik_batched_sum(
+            _ptr(Xd), _ptr(yd), offs.ctypes.data_as(ctypes.c_void_p), K, p,
+            int(bool(fit_intercept)), _ptr(cd), _ptr(sd), _ptr(bd), g, _ptr(out), _ptr(total),
+            _stream(dev))
+        _hip.check(rc, "dlsa_logistic_loglik_batched_sum")
+
+    return _loglik_groups(call, betas, p + (1 if fit_intercept else 0), K, dev, return_sum)
+
+
+def logistic_loglik_batched_categorical(Xn, codes, y, offsets, levels, betas, fit_intercept=False,
+                                        center=None, scale=None, rows_per_chunk=0, device=None,
+                                        return_sum=False):
+    """``logistic_loglik_batched`` on the categorical-code layout of
+    ``logistic_model_batched_categorical`` (same Xn / codes / levels / center /
+    scale and parameter order): the log-likelihood of the dummy-expanded design
+    without building it -- 8 q + F + 8 bytes per row, the dummy coefficients a
+    table in LDS (``dlsa_logistic_loglik_categorical``).  betas: [B, P]; more
+    than 16 candidates are evaluated 16 to a pass.  Returns a [K, B] fp64
+    device tensor, with ``return_sum`` also its [B] sum over the partitions.
+    A code >= levels[f] raises ``DlsaHipError``."""
+    dev = _require_gpu(device)
+    Xd, cd8, yd, offs, lv, cen, sca = _cat_inputs(Xn, codes, y, offsets, levels, center, scale,
+                                                  dev)
+    q, F, K = Xd.shape[1], cd8.shape[1], offs.size - 1
+    lib = _hip.load()
+
+    def call(bd, g, out, total):
+        rc = lib.dlsa_logistic_loglik_categorical(
+            _ptr(Xd), _ptr(cd8), _ptr(yd), offs.ctypes.data_as(ctypes.c_void_p), K, q, F,
+            lv.ctypes.data_as(ctypes.c_void_p), int(bool(fit_intercept)), _ptr(cen), _ptr(sca),
+            _ptr(bd), g, int(rows_per_chunk), _ptr(out), _ptr(total), _stream(dev))
+        _hip.check(rc, "dlsa_logistic_loglik_categorical")
+
+    P = int(bool(fit_intercept)) + q + int((lv - 1).sum())
+    return _loglik_groups(call, betas, P, K, dev, return_sum)
 
 
 # ---------------------------------------------------------------------------
@@ -637,9 +697,33 @@ def logistic_model_eval(sample_df, Y_name, par, fit_intercept=False, dummy_info=
     method, e.g. beta_byAIC / beta_byBIC / beta_byOLS / beta_byONESHOT).
     Returns a one-row DataFrame with the same columns.  A partition missing a
     dummy level is evaluated with that dummy column set to 0, as the
-    reference does (models.py:185-193).  The pass runs on the GPU."""
+    reference does (models.py:185-193).  The pass runs on the GPU; with
+    ``dummy_info`` on the categorical-code layout (no dense dummy matrix)
+    while the design is within that kernel's limits."""
     import pandas as pd
 
+    betas = np.ascontiguousarray(np.asarray(par, dtype=np.float64).T)
+    base = set(dummy_factors_baseline)
+    # uint8 codes: at most 255 dummy columns per factor, else the dense design
+    if len(dummy_info) > 0 and all(sum(c not in base for c in names) <= 255
+                                   for names in dummy_info["factor_selected_names"].values()):
+        enc = encode_categorical(sample_df, Y_name, dummy_info, dummy_factors_baseline)
+        q, F = enc["Xn"].shape[1], enc["codes"].shape[1]
+        P = int(bool(fit_intercept)) + len(enc["cols"])
+        if F <= 16 and int(bool(fit_intercept)) + q <= 16 and P <= _hip.MAX_P:
+            if enc["unknown"] or (enc["counts"] == 0).any():
+                absent = [c for c, m in zip(enc["cols"][q:], enc["counts"]) if m == 0]
+                warnings.warn("Dummies:" + str(set(absent)) + "missing in this data chunk "
+                              + str((len(sample_df), len(enc["cols"]))))
+            center = scale = None
+            if len(data_info) > 0 and q > 0:
+                center = np.array([_describe_row(data_info, c, 1) for c in enc["numeric"]])
+                scale = np.array([_describe_row(data_info, c, 2) for c in enc["numeric"]])
+            y = np.asarray(sample_df[Y_name], dtype=np.float64)
+            ll = logistic_loglik_batched_categorical(
+                enc["Xn"], enc["codes"], y, np.array([0, y.size]), enc["levels"], betas,
+                fit_intercept=fit_intercept, center=center, scale=scale)
+            return pd.DataFrame(ll.cpu().numpy(), columns=list(par.columns))
     x_train, numeric, cols, missing = _design(sample_df, Y_name, dummy_info, dummy_factors_baseline)
     if missing:
         warnings.warn("Dummies:" + str(set(cols) - set(x_train.columns))
@@ -655,7 +739,6 @@ def logistic_model_eval(sample_df, Y_name, par, fit_intercept=False, dummy_info=
             if c in numeric:
                 center[j] = _describe_row(data_info, c, 1)
                 scale[j] = _describe_row(data_info, c, 2)
-    betas = np.ascontiguousarray(np.asarray(par, dtype=np.float64).T)
     ll = logistic_loglik_batched(X, y, np.array([0, X.shape[0]]), betas,
                                  fit_intercept=fit_intercept, center=center, scale=scale)
     return pd.DataFrame(ll.cpu().numpy(), columns=list(par.columns))

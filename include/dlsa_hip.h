@@ -289,6 +289,45 @@ int dlsa_logistic_fit_categorical(const double* Xn, const uint8_t* codes, const 
                                   int32_t* iters, int32_t* status,
                                   const dlsa_fit_options* opt, void* stream);
 
+/*
+ * dlsa_logistic_loglik_batched with the job-level total of the reference's
+ * second pass (the group-by sum of dlsa/model_eval.py:38):
+ *   loglik_sum[b] = sum_k loglik[k * n_beta + b], k ascending, from one small
+ * kernel (bit-identical run to run).  loglik_sum [n_beta] device or NULL.
+ */
+int dlsa_logistic_loglik_batched_sum(const double* X, const double* y,
+                                     const int64_t* offsets, int32_t K, int32_t p,
+                                     int32_t fit_intercept, const double* center,
+                                     const double* scale, const double* betas,
+                                     int32_t n_beta, double* loglik, double* loglik_sum,
+                                     void* stream);
+
+/*
+ * Log-likelihood evaluation pass on the categorical-code layout of
+ * dlsa_logistic_fit_categorical (Xn, codes, levels, center / scale of the
+ * numeric columns, parameter order as there): for every partition k and
+ * candidate b
+ *   eta_i = beta_b[0] (intercept) + sum_j (x_ij - c_j) / s_j beta_b[ic + j]
+ *           + sum_f (code_if > 0 ? beta_b[dummy column code_if of factor f] : 0)
+ *   loglik[k * n_beta + b] = sum_i y_i eta_i - log(1 + exp(eta_i)),
+ * the value dlsa_logistic_loglik_batched gives on the dummy-expanded design,
+ * from 8 q + F + 8 bytes per row instead of 8 P + 8.  The dummy coefficients
+ * are a table in LDS; no atomics: bit-identical run to run.  loglik_sum
+ * [n_beta] (device or NULL) = sum_k loglik[k, .] in k order.  An empty
+ * partition gives 0.  rows_per_chunk = 0: the plan's default.  Codes >=
+ * levels[f] fail the call with DLSA_E_INVALID (they are never used as an
+ * index).  Limits: F <= 16, levels[f] in 1..256, fit_intercept + q <= 16,
+ * P <= DLSA_MAX_P, 1 <= n_beta <= 16.  levels is a HOST array [F]; betas
+ * [n_beta, P] device.  Synchronises the stream.
+ */
+int dlsa_logistic_loglik_categorical(const double* Xn, const uint8_t* codes, const double* y,
+                                     const int64_t* offsets, int32_t K, int32_t q, int32_t F,
+                                     const int32_t* levels, int32_t fit_intercept,
+                                     const double* center, const double* scale,
+                                     const double* betas, int32_t n_beta,
+                                     int32_t rows_per_chunk, double* loglik,
+                                     double* loglik_sum, void* stream);
+
 /* Timing/iteration record of the calling thread's last fit. */
 int dlsa_last_fit_stats(dlsa_fit_stats* out);
 

@@ -47,6 +47,10 @@ for v in "$@"; do
     ozpd2prof) D="DLSA_OZ_PDMA=2 -DDLSA_OZ_PROF=1" ;;
     ozovl) D="DLSA_OZ_OVL=1" ;;
     ozquad) D="DLSA_OZ_R4=0 -DDLSA_OZ_EDGE=0" ;;
+    ev256x3) D="DLSA_EVALCAT_RB=256 -DDLSA_EVALCAT_NSLOT=3" ;;
+    ev128x2) D="DLSA_EVALCAT_RB=128 -DDLSA_EVALCAT_NSLOT=2" ;;
+    ev128x3) D="DLSA_EVALCAT_RB=128 -DDLSA_EVALCAT_NSLOT=3" ;;
+    ev64x2) D="DLSA_EVALCAT_RB=64 -DDLSA_EVALCAT_NSLOT=2" ;;
     knobs) D=DLSA_ENV_KNOBS=1 ;;
     nospec) D=DLSA_SPEC_PASS=0 ;;
     ozs1) D=DLSA_OZ_SCHED=1 ;;
@@ -84,6 +88,7 @@ for v in "$@"; do
     olsks2k) ONLY='["ols_stream.hip", "capi.hip"]' ;;
     wn*|wrow*) ONLY='["wide_pass.hip"]' ;;
     knobs|nospec) ONLY='["capi.hip"]' ;;
+    ev*) ONLY='["eval_cat_pass.hip"]' ;;
     cmabl) ONLY='["irls_coop_g1.hip", "irls_coop_g2.hip", "irls_coop_g3.hip", "irls_coop_g4.hip", "irls_coop_g5.hip", "irls_coop_g6.hip"]' ;;
     ols*|wslot3) ONLY='["irls_wave.hip", "irls_wave_g2.hip"]' ;;
   esac
