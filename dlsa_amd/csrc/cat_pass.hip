@@ -35,7 +35,7 @@
 //
 // The pass writes the same per-chunk partial slab (lower-triangle 16x16
 // tiles, gradient, log-likelihood) as the dense fused pass, so the Newton
-// solve, warm-start levels and phases are shared (capi.hip).
+// solve, warm-start levels and phases are shared (fit_cat.hip, fit_driver.hpp).
 #include <math.h>
 
 #include "dlsa_internal.hpp"
@@ -69,8 +69,8 @@ namespace dlsa {
 // |x| < 2^51, x + 1.5 * 2^52 has ulp 1, so one FMA rounds v * scale (exactly,
 // once) and the low bits of the sum minus those of 1.5 * 2^52 are the
 // integer -- an FMA and a 64-bit integer subtraction instead of the emulated
-// f64 -> i64 conversion (7 VALU ops, 5 of them fp64).  The grids (capi.hip
-// fit_categorical) bound every term by 2^50.
+// f64 -> i64 conversion (7 VALU ops, 5 of them fp64).  The grids (fit_cat.hip
+// cat_grids) bound every term by 2^50.
 __device__ __forceinline__ unsigned long long fx_term(double v, double scale) {
   const double t = fma(v, scale, 6755399441055744.0);  // 1.5 * 2^52
   return (unsigned long long)__double_as_longlong(t) - 0x4338000000000000ull;

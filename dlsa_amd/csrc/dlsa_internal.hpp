@@ -26,7 +26,7 @@ enum : int32_t {
   PHASE_LEVEL_DONE = 4,
   // host-set for one launch only: a PHASE_F64 partition whose max |z| record
   // is stale, routed to the fp64-MFMA exact pass beside an int8 pass of the
-  // fresh ones (capi.hip fused_pass); restored to PHASE_F64 before the solve
+  // fresh ones (fit_fused.hip FusedFit::pass); restored to PHASE_F64 before the solve
   PHASE_F64_STALE = 5
 };
 constexpr int kRunPhases = 3;
@@ -150,7 +150,7 @@ struct SolveArgs {
 constexpr double kStallDll = 1e-5;
 // An approximate iteration whose max |step| is below kOzNearTol (1 + max|theta|)
 // is one or two iterations from the exact pass: the next bf16 pass records
-// max |sqrt(w) x| for the Ozaki digit scales (capi.hip, irls_oz_impl.hpp)
+// max |sqrt(w) x| for the Ozaki digit scales (fit_fused.hip, irls_oz_impl.hpp)
 constexpr double kOzNearTol = 1e-2;
 __device__ __forceinline__ int32_t escalate_phase(const SolveArgs& a, int32_t ph) {
   return ph == PHASE_F32 ? a.escalate_to : PHASE_F64;
@@ -413,6 +413,9 @@ hipError_t launch_column_moments(const double* X, int64_t n, int p, double* out,
                                  int G, int64_t rows_per_range, hipStream_t s);
 void column_moments_plan(int64_t n, int p, int* G, int64_t* rows_per_range);
 
+// The calling thread's last error text and last fit's statistics (capi.hip).
+extern thread_local std::string g_last_error;
+extern thread_local dlsa_fit_stats g_stats;
 void set_error(const std::string& msg);
 
 // Raise a kernel's dynamic-LDS limit to `bytes` once per (kernel, device):

@@ -380,7 +380,7 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
   // OLS (w in {0, 1}): A operands are x itself (padded rows zeroed in the ring,
   // the intercept column = w)
   constexpr bool OLS_NOMUL = DLSA_WAVE_OLS_NOMUL && FAM == FAMILY_GAUSSIAN;
-  // OLS is one pass at theta = 0 (fit_impl: fit_init zeroes theta, max_iter =
+  // OLS is one pass at theta = 0 (fit_dense: fit_init zeroes theta, max_iter =
   // 1, no warm-start levels, no polish): eta = 0 and r = y, so the row phase
   // skips the x . theta dot products and their row reductions -- fp64 VALU
   // work that never co-executes with the fp64 MFMAs of the tile phase

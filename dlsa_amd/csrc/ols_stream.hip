@@ -2,7 +2,7 @@
 // linear-model path, projects/results/linear_regression_dc.py:27-37) streaming
 // X straight from HBM into the MFMA operand registers.
 //
-// The OLS fit is one pass at theta = 0 (fit_impl: max_iter 1, no warm start):
+// The OLS fit is one pass at theta = 0 (fit_dense: max_iter 1, no warm start):
 // w = 1, r = y, so a row needs no eta, no exp / log and no weight -- only
 // X^T X (fp64 MFMA), X^T y and -y^2 / 2.  The per-wave LDS-DMA kernel
 // (irls_wave_impl.hpp) staged every 8-row block through an LDS ring, at a

@@ -131,7 +131,7 @@ typedef struct dlsa_fit_options {
 /* The library reads no environment variable that changes a result: the
  * output of every entry point depends only on its arguments.  (DLSA_TRACE
  * prints per-iteration steps to stderr; profiling builds compiled with
- * -DDLSA_ENV_KNOBS=1 also read the A/B knobs named in capi.hip.) */
+ * -DDLSA_ENV_KNOBS=1 also read the A/B knobs named in csrc/fit_plan.hpp and the fit_*.hip files.) */
 
 typedef struct dlsa_fit_stats {
   int32_t iterations;       /* Newton iterations run (max over partitions) */
@@ -278,7 +278,10 @@ int dlsa_logistic_loglik_batched(const double* X, const double* y,
  * fail the call with DLSA_E_INVALID.  Limits: F <= 16, levels[f] in 1..256,
  * fit_intercept + q <= 16.  levels is a HOST array [F]; opt may be NULL
  * (hessian_mode is ignored: every pass is exact; warm_start runs a 1/16-prefix
- * level first only when the partitions average >= 2^19 rows).
+ * level first only when the partitions average >= 2^19 rows).  Workspace:
+ * there is no size query for this layout; opt->workspace is used when it is
+ * large enough, and when it is NULL or too small the call allocates its own
+ * (stream-ordered) instead of returning DLSA_E_WORKSPACE.
  */
 int dlsa_logistic_fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
                                   const int64_t* offsets, int32_t K, int32_t q, int32_t F,

@@ -34,6 +34,51 @@ def test_library_exports_every_header_symbol():
     assert b"gfx950" in _hip.load().dlsa_build_info()
 
 
+# (partition sizes, p, fit_intercept, rows_per_chunk) -> bytes, recorded at
+# commit 3c20193 (before the planning moved to csrc/fit_plan.hpp)
+_WORKSPACE_BYTES = [
+    ([8000, 5001], 100, 1, 1500, 599808),
+    ([10000000, 100000, 100000], 511, 1, 0, 440327680),
+    ([6000] * 5, 260, 1, 0, 89432064),
+    ([4000, 0, 150, 3500], 220, 0, 700, 17782784),
+    ([97656] * 1024, 100, 1, 0, 366002944),
+    ([5000000, 60000, 60000], 512, 0, 0, 13506893824),
+    ([6000, 5000], 191, 1, 0, 337664),  # P = 192, fused
+    ([6000, 5000], 192, 1, 0, 20060160),  # P = 193, wide
+    ([0, 0], 3, 0, 0, 6400),
+    ([1], 0, 1, 0, 6400),
+    ([156250] * 64, 500, 0, 0, 564883712),
+    ([976563] * 8, 64, 0, 0, 27397888),
+    ([40000, 36000], 12, 0, 40000, 8448),
+]
+
+
+def _workspace_bytes(offsets, p, fit_intercept, rows_per_chunk):
+    import ctypes
+
+    from dlsa_amd import _hip
+
+    lib = ctypes.CDLL(_hip.LIB_PATH)
+    fn = lib.dlsa_logistic_workspace_bytes
+    fn.restype = ctypes.c_int64
+    fn.argtypes = [ctypes.POINTER(ctypes.c_int64)] + [ctypes.c_int32] * 4
+    off = (ctypes.c_int64 * len(offsets))(*offsets)
+    return fn(off, len(offsets) - 1, p, fit_intercept, rows_per_chunk)
+
+
+@pytest.mark.parametrize("sizes,p,fi,rpc,want", _WORKSPACE_BYTES)
+def test_workspace_bytes_table(sizes, p, fi, rpc, want):
+    """Every layout offset and every plan's chunk count (make_plan, the wide
+    plans and their levels, both layouts) feeds the total: the planning
+    arithmetic is pinned without a GPU."""
+    offsets = [0] + [int(v) for v in np.cumsum(sizes)]
+    assert _workspace_bytes(offsets, p, fi, rpc) == want
+
+
+def test_workspace_bytes_rejects_decreasing_offsets():
+    assert _workspace_bytes([0, 5, 3], 10, 1, 0) == -1
+
+
 def test_fit_fails_loudly_without_gpu():
     import torch
 

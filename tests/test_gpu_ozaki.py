@@ -413,7 +413,7 @@ def test_ozaki_polish_pass_per_entry(torch_cuda, M, monkeypatch, kind):
     (advisor finding, r4) -- on the outlier design that left 8e-5 per entry
     (round-5 run r05k).  The exact pass therefore runs on the int8 cores only
     when every partition in it has a record from its last approximate pass
-    (capi.hip zfresh), else on the fp64 MFMA.  Per entry within 1e-10 of the
+    (fit_fused.hip zfresh), else on the fp64 MFMA.  Per entry within 1e-10 of the
     fp64-MFMA pass at the same iterate."""
     X, y = heavy_design(kind, 24000, seed=4, p_extra=6)  # P = 13: the in-place images fit
     off = np.array([0, 7000, 15000, 24000])

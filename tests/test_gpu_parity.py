@@ -153,6 +153,30 @@ def test_shapes_vs_oracle(torch_cuda, M, p, fi):
     assert _rel(fit.loglik.cpu(), ll) < 1e-10
 
 
+@pytest.mark.parametrize("p,fi,sizes,check", [(12, True, [6000, 5000, 0], (0, 1)),
+                                              (200, False, [30000, 26000], (1,))])
+def test_warm_start_level_runs_vs_oracle(torch_cuda, M, p, fi, sizes, check):
+    """The smallest fits in which a warm-start level runs, on the fused and
+    the wide path.  Fused: the level's floor is max(2048, 64 * 13) = 2048 rows
+    per non-empty partition, 4096 <= 11000 / 2, so the 1/16 level runs.  Wide:
+    the floor is 64 * 200 = 12800, 25600 <= 28000; the 1/4 level has the same
+    rows and replaces the 1/16 one, so exactly one level runs.  A level's
+    approximate passes stream a prefix: fewer rows than passes x n."""
+    n = sum(sizes)
+    X, y = O.simulate_counter(n, p, seed=p + 3)
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    fit = M.logistic_model_batched(X, y, off, fit_intercept=fi)
+    st = fit.status.cpu().numpy()
+    for k, nk in enumerate(sizes):  # an empty partition reports DLSA_STATUS_EMPTY (3)
+        assert st[k] == (0 if nk else 3)
+    assert fit.stats["passes_fp32"] > 0
+    assert fit.stats["rows_fp32"] < fit.stats["passes_fp32"] * n
+    for k in check:
+        o = O.logistic_fit(X[off[k]:off[k + 1]], y[off[k]:off[k + 1]], fit_intercept=fi)
+        assert _rel(fit.theta[k].cpu(), o["coef"]) < REL
+        assert _rel(fit.sig_inv[k].cpu(), o["Sig_inv"]) < REL
+
+
 def test_misaligned_x_view(torch_cuda, M):
     """X starting 8 bytes off a 16-byte boundary (LDS-DMA shift path)."""
     torch = torch_cuda

@@ -151,7 +151,7 @@ def test_config3_reference_partition_policy(torch_cuda, M):
     fit = M.logistic_model_batched_categorical(Xn, codes, y, off, levels, fit_intercept=True)
     assert (fit.status.cpu().numpy() == 0).all(), fit.status_counts()
     # partitions of >= 2^19 rows run a 1/16-prefix warm-start level first
-    # (capi.hip fit_categorical): some passes streamed fewer than all n rows
+    # (fit_cat.hip fit_categorical): some passes streamed fewer than all n rows
     st = fit.stats
     assert st["rows_fp64"] < st["passes_fp64"] * n, st
     Xd = M.expand_categorical(Xn, codes, levels)
@@ -208,7 +208,7 @@ def test_config4_partition_size(torch_cuda, M):
 def test_wide_skewed_partitions_level_plans(torch_cuda, M):
     """Wide path (P = 512) with skewed partition sizes, n_k = [5e6, 6e4, 6e4]:
     the 1/16 warm-start level then has MORE Gram row groups (258) than the
-    all-rows plan (256), the case the workspace is sized for (capi.hip
+    all-rows plan (256), the case the workspace is sized for (fit_plan.hpp
     make_wide_layout over every level plan).  The small partitions against
     the oracle; the big one through the score equation."""
     torch = torch_cuda

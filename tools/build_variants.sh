@@ -79,15 +79,18 @@ for v in "$@"; do
     *) echo "unknown variant $v"; exit 1 ;;
   esac
   ONLY=None
+  # the planning header (fit_plan.hpp: env_knob, DLSA_CAT_ND_CAP) is compiled into all of these
+  HOST='"fit_fused.hip", "fit_wide.hip", "fit_cat.hip", "capi.hip"'
   case $v in
     oz*|ozs*) ONLY='["irls_oz.hip", "irls_oz_g2.hip"]' ;;
     solve*) ONLY='["newton_solve.hip"]' ;;
-    catnd*) ONLY='["capi.hip"]' ;;
+    catnd*) ONLY="[$HOST]" ;;
     cat*) ONLY='["cat_pass.hip"]' ;;
     olswave|olspf4|olspf3|olspf2|olsks2|olsks8|olsks12|olsks16) ONLY='["ols_stream.hip"]' ;;
-    olsks2k) ONLY='["ols_stream.hip", "capi.hip"]' ;;
+    olsks2k) ONLY="[\"ols_stream.hip\", $HOST]" ;;
     wn*|wrow*) ONLY='["wide_pass.hip"]' ;;
-    knobs|nospec) ONLY='["capi.hip"]' ;;
+    knobs) ONLY="[$HOST]" ;;
+    nospec) ONLY='["fit_fused.hip"]' ;;
     ev*) ONLY='["eval_cat_pass.hip"]' ;;
     cmabl) ONLY='["irls_coop_g1.hip", "irls_coop_g2.hip", "irls_coop_g3.hip", "irls_coop_g4.hip", "irls_coop_g5.hip", "irls_coop_g6.hip"]' ;;
     ols*|wslot3) ONLY='["irls_wave.hip", "irls_wave_g2.hip"]' ;;
