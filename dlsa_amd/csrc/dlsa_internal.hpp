@@ -136,54 +136,12 @@ struct SolveArgs {
   int32_t eval_only;    // polish: publish Sig_inv / loglik at the current theta, no step
 };
 
-// Stall detection of the approximate phases (newton_solve.hip,
-// wide_pass.hip).  With an approximate Hessian H~ and the exact gradient,
-// Newton contracts at rate ~ ||I - H~^-1 H|| (about kappa 2^-8 for bf16): on
-// an ill-conditioned design that rate nears 1 and the fit would crawl to
-// max_iter.  Far from the MLE (Newton's damped phase) steps of similar size
-// are normal whatever the Hessian precision, so evidence is only taken once
-// the log-likelihood has gone quiet (the last step gained at most
-// kStallDll (1 + |ll|)): there an approximate iteration "stalls" when its max
-// |step| did not at least halve against the previous one, or when it
-// backtracks; two stalls in a row move the partition one precision up
-// (F32 -> escalate_to, F32X -> F64).  Returns the phase to continue in.
-constexpr double kStallDll = 1e-5;
+// Step control of the Newton update (stall escalation, step halving,
+// convergence): newton_step.hpp.
 // An approximate iteration whose max |step| is below kOzNearTol (1 + max|theta|)
 // is one or two iterations from the exact pass: the next bf16 pass records
 // max |sqrt(w) x| for the Ozaki digit scales (fit_fused.hip, irls_oz_impl.hpp)
 constexpr double kOzNearTol = 1e-2;
-__device__ __forceinline__ int32_t escalate_phase(const SolveArgs& a, int32_t ph) {
-  return ph == PHASE_F32 ? a.escalate_to : PHASE_F64;
-}
-__device__ __forceinline__ int32_t approx_stall_step(const SolveArgs& a, int k, int32_t ph,
-                                                     bool stalled) {
-  const int st = stalled ? a.stall[k] + 1 : 0;
-  if (st >= 2) {
-    a.stall[k] = 0;
-    a.dm_prev[k] = 0.0;
-    return escalate_phase(a, ph);
-  }
-  a.stall[k] = st;
-  return ph;
-}
-// Approximate-phase iteration with a step of max |d| = dm (not yet below
-// switch_tol): log-likelihood ll at the pass's point, llp at the previous one.
-__device__ __forceinline__ int32_t approx_next_phase(const SolveArgs& a, int k, int32_t ph,
-                                                     double dm, double ll, double llp) {
-  if (!(ll - llp <= kStallDll * (1.0 + fabs(ll)))) {  // damped phase (or first iteration)
-    a.stall[k] = 0;
-    a.dm_prev[k] = 0.0;
-    return ph;
-  }
-  const double dp = a.dm_prev[k];
-  const int32_t nph = approx_stall_step(a, k, ph, dp > 0.0 && dm > 0.5 * dp);
-  if (nph == ph) a.dm_prev[k] = dm;
-  return nph;
-}
-// A backtracking approximate iteration: a stall only once the fit was quiet.
-__device__ __forceinline__ int32_t approx_backtrack_phase(const SolveArgs& a, int k, int32_t ph) {
-  return a.dm_prev[k] > 0.0 ? approx_stall_step(a, k, ph, true) : ph;
-}
 
 // Arguments of the log-likelihood evaluation pass.
 struct EvalArgs {
@@ -202,7 +160,7 @@ struct EvalArgs {
   int32_t nslot, slot_bytes;
 };
 
-// Wide-P path (DLSA_MAX_P_FUSED < P <= DLSA_MAX_P, wide_pass.hip): a row
+// Wide-P path (DLSA_MAX_P_FUSED < P <= DLSA_MAX_P, wide_exact.hip): a row
 // pass (eta, weights, gradient, log-lik) and a separate Gram pass over
 // 128x128 output tiles of the padded PP = 128 * NB Hessian.
 constexpr int kWideTile = 128;

@@ -1,4 +1,4 @@
-// The wide fit (P > DLSA_MAX_P_FUSED, wide_pass.hip): per Newton iteration the
+// The wide fit (P > DLSA_MAX_P_FUSED, wide_common.hpp): per Newton iteration the
 // fused bf16 pass (PHASE_F32 partitions) and/or the row + exact Gram passes
 // (PHASE_F64), the deterministic partial-tile assembly and the per-partition
 // blocked-Cholesky update.  Same warm-start levels, phases, state machine and

@@ -12,11 +12,13 @@
 //      pass was evaluated) and the log-likelihood;
 //   4. Cholesky H = L L^T in LDS, solve L L^T d = g, theta += d;
 //   5. convergence / phase switch (approximate Hessian -> fp64 pass), stall
-//      escalation (bf16 -> fp32 -> fp64, dlsa_internal.hpp).
+//      escalation (bf16 -> fp32 -> fp64).
+// The step control (2, 5 and the failure exits) is newton_step.hpp, shared
+// with wide_newton.hip.
 // eval_only (the polish pass after a budget ran out): steps 1 and 3 only.
 #include <math.h>
 
-#include "dlsa_internal.hpp"
+#include "newton_step.hpp"
 
 // Newton steps refining v_rsq_f64 in the diagonal-block factor (A/B builds)
 #ifndef DLSA_SOLVE_RSQ_STEPS
@@ -48,17 +50,6 @@ constexpr int kRedFlag = kMaxSolveWaves, kRedSink = kMaxSolveWaves + 1,
               kRedLL = kMaxSolveWaves + 2, kRedZero = kMaxSolveWaves + 3;
 constexpr int kRedSize = kMaxSolveWaves + 4;
 
-__device__ __forceinline__ double block_max(double v, double* red) {
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  double r = red[0];
-  for (int i = 1; i < (int)(blockDim.x >> 6); ++i) r = fmax(r, red[i]);
-  return r;
-}
-
 // Sum of 64 lanes, result in every lane.
 __device__ __forceinline__ double wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -66,13 +57,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 typedef double d4s __attribute__((ext_vector_type(4)));
-
-// v_readlane of a double (lane index wave-uniform)
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
 
 // Packed lower triangle: element (i, j), i >= j, at i (i + 1) / 2 + j.
 __device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }
@@ -92,7 +76,8 @@ __global__ __launch_bounds__(NTHR) void newton_solve_kernel(const SolveArgs a) {
                                      // on the diagonal, at LDS offset 0: compile-time
                                      // addresses in the panel solve (packed-triangle
                                      // addresses of a moving panel, or a P-dependent base,
-                                     // cost ~140 spilled SGPRs)
+                                     // cost ~140 spilled SGPRs); after the factor, the
+                                     // reduction scratch of step 6
   double* H = sm + 256;              // packed lower triangle, P (P + 1) / 2
   double* g = H + P * (P + 1) / 2;   // PP
   double* z = g + PP;                // PP
@@ -163,48 +148,10 @@ __global__ __launch_bounds__(NTHR) void newton_solve_kernel(const SolveArgs a) {
   __syncthreads();
   const double ll = red[kRedLL];
   const int it = a.iters[k];
-  double* th = a.theta + (int64_t)k * P;
 
-  // a warm-start level that fails (separation, too few rows) only restarts
-  // the partition from theta = 0 on the next level
-  auto level_fail = [&]() {
-    for (int f = tid; f < P; f += kSolveThreads) th[f] = 0.0;
-    if (tid == 0) {
-      a.phase[k] = PHASE_LEVEL_DONE;
-      a.iters[k] = it + 1;
-    }
-  };
-  if (!isfinite(ll)) {
-    if (a.subsample)
-      level_fail();
-    else if (tid == 0)
-      a.status[k] = DLSA_STATUS_NONFINITE;
-    return;
-  }
-
-  // 2. step halving on a log-likelihood decrease ---------------------------
-  //    threshold above the fp32-log noise of mixed-mode log-likelihoods; real
-  //    overshoots of a Newton step lose far more than 1e-6 relative
+  // 2. non-finite log-likelihood, step halving on a decrease ---------------
   const double llp = a.ll_prev[k];
-  if (!a.eval_only && a.family == FAMILY_LOGISTIC && it > 0 &&
-      ll < llp - 1e-6 * (1.0 + fabs(llp)) && a.backtracks[k] < 40) {
-    const int bt = a.backtracks[k] + 1;
-    const double sc = ldexp(1.0, -bt);
-    const double* tp = a.theta_prev + (int64_t)k * P;
-    const double* dp = a.delta_prev + (int64_t)k * P;
-    for (int f = tid; f < P; f += kSolveThreads) th[f] = tp[f] + sc * dp[f];
-    if (tid == 0) {
-      a.backtracks[k] = bt;
-      a.iters[k] = it + 1;
-      int ph = phase;
-      if (!a.subsample && ph != PHASE_F64) {  // an approximate step that overshot
-        ph = approx_backtrack_phase(a, k, ph);
-        a.phase[k] = ph;
-      }
-      atomicAdd(&a.counters[ph], 1);
-    }
-    return;
-  }
+  if (!step_prelude<kSolveThreads>(a, k, phase, it, ll, llp)) return;
 
   SOLVE_MARK(1)
   // 3. publish the information matrix at the evaluation point --------------
@@ -263,7 +210,7 @@ __global__ __launch_bounds__(NTHR) void newton_solve_kernel(const SolveArgs a) {
 #pragma unroll
       for (int kk = 0; kk < 16; ++kk) {
         if (kk < nb) {  // wave-uniform
-          const double dkk = readlane_f64(av[kk], kk);
+          const double dkk = bcast_f64(av[kk], kk);
           good = good && dkk > 0.0 && isfinite(dkk);
           // 1 / sqrt(d) by v_rsq_f64 + two Newton steps (~1 ulp), L_kk = d / sqrt(d):
           // the serial chain of the block is 16 of these (IEEE sqrt + division:
@@ -276,7 +223,7 @@ __global__ __launch_bounds__(NTHR) void newton_solve_kernel(const SolveArgs a) {
           av[kk] = (i > kk) ? av[kk] * il : (i == kk ? lkk : av[kk]);
 #pragma unroll
           for (int j = kk + 1; j < 16; ++j) {
-            const double ljk = readlane_f64(av[kk], j);  // L[j][kk], row j's lane
+            const double ljk = bcast_f64(av[kk], j);  // L[j][kk], row j's lane
             if (j <= i) av[j] = fma(-av[kk], ljk, av[j]);
           }
           if (lv == 0) invd[c0 + kk] = il;
@@ -366,24 +313,7 @@ __global__ __launch_bounds__(NTHR) void newton_solve_kernel(const SolveArgs a) {
     SOLVE_PAN(3)
   }
   if (!ok) {
-    if (a.subsample) {
-      level_fail();
-      return;
-    }
-    if (tid == 0) {
-      if (phase != PHASE_F64 && a.family == FAMILY_LOGISTIC) {
-        // low-precision Hessian lost definiteness: redo this point one
-        // precision up (bf16 -> fp32 -> fp64)
-        const int32_t ph = escalate_phase(a, phase);
-        a.phase[k] = ph;
-        a.iters[k] = it + 1;
-        a.stall[k] = 0;
-        a.dm_prev[k] = 0.0;
-        atomicAdd(&a.counters[ph], 1);
-      } else {
-        a.status[k] = DLSA_STATUS_SINGULAR;
-      }
-    }
+    factor_failed<kSolveThreads>(a, k, phase, it);
     return;
   }
 
@@ -412,7 +342,7 @@ __global__ __launch_bounds__(NTHR) void newton_solve_kernel(const SolveArgs a) {
 #pragma unroll
       for (int kk = 15; kk >= 0; --kk) {
         if (kk < nb) {  // wave-uniform
-          const double dk = readlane_f64(zi * il, kk);
+          const double dk = bcast_f64(zi * il, kk);
           zi = (i == kk) ? dk : fma(-lc[kk], dk, zi);
         }
       }
@@ -436,91 +366,9 @@ __global__ __launch_bounds__(NTHR) void newton_solve_kernel(const SolveArgs a) {
            "trailing %lld) trisolve %lld\n", P, tmark[1] - tmark[0], tmark[2] - tmark[1],
            tmark[3] - tmark[2], tpan[0], tpan[1], tpan[2], tmark[4] - tmark[3]);
 #endif
-  // 6. update + convergence ------------------------------------------------
-  double dm = 0.0, tm = 0.0, tg = 0.0;
-  double* tp = a.theta_prev + (int64_t)k * P;
-  double* dp = a.delta_prev + (int64_t)k * P;
-  for (int f = tid; f < P; f += kSolveThreads) {
-    const double d = z[f];
-    const double t0 = th[f];
-    const double t1 = t0 + d;
-    tp[f] = t0;
-    dp[f] = d;
-    th[f] = t1;
-    dm = fmax(dm, fabs(d));
-    tm = fmax(tm, fabs(t1));
-    tg += t1 * g[f];
-  }
-  dm = block_max(dm, red);
-  tm = block_max(tm, red);
-  if (!isfinite(dm) && !a.subsample) {
-    // keep the last finite iterate (each thread restores the entries it
-    // wrote): the status reports the failure and the combine step excludes
-    // the partition
-    for (int f = tid; f < P; f += kSolveThreads) th[f] = tp[f];
-  }
-  if (a.family == FAMILY_GAUSSIAN) {
-    // OLS: theta was 0, one Newton step is the closed form (X^T X)^-1 X^T y;
-    // residual sum of squares = y^T y - theta^T X^T y = -2 ll(0) - theta . g
-    tg = wave_sum(tg);
-    __syncthreads();
-    if (lane == 0) red[wid] = tg;
-    __syncthreads();
-    if (tid == 0) {
-      double tgs = 0.0;
-#pragma unroll
-      for (int w = 0; w < kSolveWaves; ++w) tgs += red[w];
-      a.loglik[k] = -2.0 * ll - tgs;
-      a.iters[k] = it + 1;
-      a.status[k] = isfinite(dm) ? DLSA_STATUS_OK : DLSA_STATUS_NONFINITE;
-      a.phase[k] = PHASE_DONE;
-    }
-    return;
-  }
-  if (a.subsample) {
-    if (!isfinite(dm)) {
-      level_fail();
-      return;
-    }
-    if (tid == 0) {
-      a.ll_prev[k] = ll;
-      a.backtracks[k] = 0;
-      a.iters[k] = it + 1;
-      if (dm <= a.level_tol * (1.0 + tm)) {
-        a.phase[k] = PHASE_LEVEL_DONE;
-      } else {
-        atomicAdd(&a.counters[phase], 1);
-      }
-    }
-    return;
-  }
-  if (tid == 0) {
-    a.ll_prev[k] = ll;
-    a.backtracks[k] = 0;
-    a.iters[k] = it + 1;
-    int ph = phase;
-    if (!isfinite(dm)) {
-      a.status[k] = DLSA_STATUS_NONFINITE;
-      return;
-    }
-    if (ph != PHASE_F64) {
-      if (dm <= a.switch_tol * (1.0 + tm)) {
-        ph = PHASE_F64;
-      } else {
-        ph = approx_next_phase(a, k, ph, dm, ll, llp);
-        // near the switch: the next bf16 pass records the Ozaki digit scales
-        if (ph == PHASE_F32 && dm <= kOzNearTol * (1.0 + tm)) atomicAdd(&a.counters[3], 1);
-      }
-    } else if (dm <= a.tol * (1.0 + tm)) {
-      a.status[k] = DLSA_STATUS_OK;
-      a.phase[k] = PHASE_DONE;
-      return;
-    }
-    a.phase[k] = ph;
-    atomicAdd(&a.counters[ph], 1);
-  }
+  // 6. update + convergence (dblk: free since the factor) -------------------
+  step_update<kSolveThreads, true>(a, k, phase, it, ll, llp, z, g, dblk);
 }
-
 
 // Sum the per-chunk partials (Hessian tiles, gradient, log-likelihood) of
 // every running partition into its first chunk's slab, in chunk order

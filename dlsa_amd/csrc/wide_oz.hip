@@ -6,7 +6,7 @@
 // Replaces, for the exact Newton iterations of a wide fit, the Sig_inv =
 // X^T diag(p(1-p)) X of the reference map stage (dlsa/models.py:110-131).
 //
-//   wide_row_kernel      (wide_pass.hip) also records per row chunk the max
+//   wide_row_kernel      (wide_exact.hip) also records per row chunk the max
 //                        |z| = |sqrt(w) x| of every feature (WideArgs::slab_zmax)
 //   wide_oz_scale_kernel per Gram row group and feature E_f with |z| < 2^E_f
 //                        (max over the row chunks that overlap the group: a

@@ -10,7 +10,7 @@
   airline-like columns (the reference standardises only when data_info is
   given, models.py:99-101) and near-collinear columns.  Default (mixed) mode
   must end status ok at 1e-8 of the oracle; a stalled partition escalates
-  bf16 -> fp32 -> fp64 (dlsa_internal.hpp).
+  bf16 -> fp32 -> fp64 (newton_step.hpp).
 * Non-finite data in one partition of a categorical fit must fail only that
   partition (the fixed-point histogram grids come from finite values).
 """
@@ -185,6 +185,25 @@ def test_default_mode_ill_conditioned_designs(torch_cuda, M, case):
     assert _rel(fit.sig_inv_theta.cpu(), St) < REL
     print(case, {k: fit.stats[k] for k in ("iterations", "passes_fp32", "passes_f32x",
                                             "passes_fp64")})
+
+
+@pytest.mark.parametrize("rho,seed", [(0.999, 12), (1 - 1e-6, 13)])
+def test_default_mode_ill_conditioned_designs_wide(torch_cuda, M, rho, seed):
+    """The same near-collinear designs on the wide path (P = 201: two 128-wide
+    column blocks, the smallest wide shape), whose Newton kernel runs the stall
+    and escalation rules of newton_step.hpp with its own factorization.
+    Hessian condition numbers 1.2e4 and 1.2e7."""
+    sizes = [14000, 15001]
+    X, y = _collinear(sum(sizes), 200, rho, seed=seed)
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    fit = M.logistic_model_batched(X, y, off, fit_intercept=True)  # default: hessian="mixed"
+    th, S, St, ll, it = O.logistic_fit_partitions(X, y, off, fit_intercept=True)
+    print({k: fit.stats[k] for k in ("iterations", "passes_fp32", "passes_f32x", "passes_fp64")},
+          _rel(fit.theta.cpu(), th), _rel(fit.sig_inv.cpu(), S), _rel(fit.sig_inv_theta.cpu(), St))
+    assert (fit.status.cpu().numpy() == 0).all(), (fit.status, fit.stats)
+    assert _rel(fit.theta.cpu(), th) < REL
+    assert _rel(fit.sig_inv.cpu(), S) < REL
+    assert _rel(fit.sig_inv_theta.cpu(), St) < REL
 
 
 def test_stalled_bf16_partition_escalates(torch_cuda, M):

@@ -25,7 +25,6 @@ for v in "$@"; do
     catrin) D=DLSA_CAT_RINNER=1 ;;
     catpf32) D=DLSA_CAT_ABLATE=32 ;;
     solveprof) D=DLSA_SOLVE_PROFILE=1 ;;
-    solveblk) D=DLSA_SOLVE_BLOCKED=1 ;;
     solversq1) D=DLSA_SOLVE_RSQ_STEPS=1 ;;
     solversq0) D=DLSA_SOLVE_RSQ_STEPS=0 ;;
     cat31) D=DLSA_CAT_ABLATE=31 ;;
@@ -58,7 +57,6 @@ for v in "$@"; do
     oz6) D=DLSA_OZ_LEVELS=6 ;;
     cmabl) D=DLSA_CM_ABLATE=1 ;;
     olswave) D=DLSA_OLS_STREAM=0 ;;
-    wnold) D=DLSA_WN_LOOKAHEAD=0 ;;
     wnf64) D=DLSA_WN_F32=0 ;;
     wnldp33) D=DLSA_WN_LDP=33 ;;
     wnldp33prof) D="DLSA_WN_LDP=33 -DDLSA_WN_PROF=1" ;;
@@ -88,7 +86,9 @@ for v in "$@"; do
     cat*) ONLY='["cat_pass.hip"]' ;;
     olswave|olspf4|olspf3|olspf2|olsks2|olsks8|olsks12|olsks16) ONLY='["ols_stream.hip"]' ;;
     olsks2k) ONLY="[\"ols_stream.hip\", $HOST]" ;;
-    wn*|wrow*) ONLY='["wide_pass.hip"]' ;;
+    wn*) ONLY='["wide_newton.hip"]' ;;
+    wrow*) ONLY='["wide_exact.hip"]' ;;
+    fab1) ONLY='["wide_fused.hip"]' ;;
     knobs) ONLY="[$HOST]" ;;
     nospec) ONLY='["fit_fused.hip"]' ;;
     ev*) ONLY='["eval_cat_pass.hip"]' ;;
