@@ -48,19 +48,6 @@
 #ifndef DLSA_CAT_ABLATE
 #define DLSA_CAT_ABLATE 0
 #endif
-// Next row's loads issued under the current row's atomics (1) or at the end
-// of the iteration (0, A/B)
-#ifndef DLSA_CAT_PF
-#define DLSA_CAT_PF 1
-#endif
-// Histogram slot order: replica outermost (0: slot = replica * levels + level)
-// or innermost (1, A/B: slot = level * R + replica).  Innermost was meant to put
-// the 16 lanes of an 8-byte LDS atomic group on 16 different bank pairs for
-// the R = 16 factors; it measured slower: 5.71-5.72 vs 5.43-5.47 ms per full
-// config-3 pass, alternated on one box (profiles/r06p_cat_slot_order_ab.txt)
-#ifndef DLSA_CAT_RINNER
-#define DLSA_CAT_RINNER 0
-#endif
 
 namespace dlsa {
 
@@ -83,9 +70,12 @@ __device__ __forceinline__ long long hist_at(const unsigned long long* h, int i)
 }
 
 // histogram slot of level slot lev, replica rp of a factor record
-// {R - 1, level slots, ...}
+// {R - 1, level slots, ...}: replica outermost.  (Replica innermost, meant to
+// put the 16 lanes of an 8-byte LDS atomic group on 16 different bank pairs
+// for the R = 16 factors, measured slower: 5.71-5.72 vs 5.43-5.47 ms per full
+// config-3 pass, profiles/r06p_cat_slot_order_ab.txt)
 __device__ __forceinline__ int cat_slot(const int4 r, int lev, int rp) {
-  return DLSA_CAT_RINNER ? lev * (r.x + 1) + rp : rp * r.y + lev;
+  return rp * r.y + lev;
 }
 
 // pair index of factors f < g among F
@@ -171,7 +161,7 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(const CatArgs a) {
   for (int i = 0; i < NQ; ++i) gacc[i] = 0.0;
   const int fold = EX ? __builtin_amdgcn_readfirstlane(a.fold) : -1;
 
-  // Software-pipelined row loop (DLSA_CAT_PF, default): the next row's x,
+  // Software-pipelined row loop: the next row's x,
   // codes and y are loaded once the current row's triangle, gradient and
   // fixed-point terms are formed -- its x registers are dead by then -- so the
   // load latency runs under the current row's ~65 LDS atomics instead of
@@ -278,11 +268,9 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(const CatArgs a) {
 #pragma unroll
     for (int i = 0; i < QN; ++i)  // parameter i is numeric column i - ic: scale hsc[2 + i - ic]
       if (i >= ic) ut[2 + i - ic] = fx_term(w * xv[i], ic ? hsc[i + 1] : hsc[i + 2]);
-#if DLSA_CAT_PF
     __builtin_amdgcn_sched_barrier(0);
     load_row(min(r + NTHR, nrows - 1));  // the next row, in flight under the atomics
     __builtin_amdgcn_sched_barrier(0);
-#endif
 
     // one-hot blocks: fixed-point histograms in LDS
     // The record of factor f + 1 (pair p + 1) is read before factor f's (pair
@@ -318,16 +306,10 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(const CatArgs a) {
         const int pn = cat_pair(f, g, FM) + 2;
         const int4 tn = ptab[pn <= kCatMaxPairs ? pn : kCatMaxPairs];
         if (!(DLSA_CAT_ABLATE & 2) && g < F && cv[f] > 0 && cv[g] > 0)
-          lds_add_u(hist + tp.x +
-                        (DLSA_CAT_RINNER ? ((cv[f] - 1) * tp.w + cv[g] - 1) * (tp.y + 1) + (lane & tp.y)
-                                         : ((lane & tp.y) * tp.z + cv[f] - 1) * tp.w + cv[g] - 1),
-                    ut[0]);
+          lds_add_u(hist + tp.x + (((lane & tp.y) * tp.z + cv[f] - 1) * tp.w + cv[g] - 1), ut[0]);
         tp = tp1;
         tp1 = tn;
       }
-#if !DLSA_CAT_PF
-    if (r + NTHR < nrows) load_row(r + NTHR);
-#endif
   }
 
   // ---- reduce the register blocks over the workgroup (fixed order) --------
@@ -428,8 +410,7 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(const CatArgs a) {
             const int4 r = ptab[cat_pair(fj, fi, FM)];
             long long s = 0;
             for (int rp = 0; rp <= r.y; ++rp)
-              s += hist_at(hist, r.x + (DLSA_CAT_RINNER ? (lj * r.w + li) * (r.y + 1) + rp
-                                                        : (rp * r.z + lj) * r.w + li));
+              s += hist_at(hist, r.x + ((rp * r.z + lj) * r.w + li));
             v = (double)s / hsl[0];
           }
         }

@@ -265,13 +265,6 @@ int ec_bp(int B) { return B <= 2 ? 2 : B <= 4 ? 4 : B <= 8 ? 8 : 16; }
 // the workgroup's LDS beside the tables; up to 4 slots while the workgroup
 // stays within half a CU's LDS (two workgroups per CU: the pass is bound by
 // the fp64 exp / log1p of every row and candidate, not only by HBM).
-// A/B builds force the block rows / ring depth (tools/build_variants.sh ev<RB>x<slots>).
-#ifndef DLSA_EVALCAT_RB
-#define DLSA_EVALCAT_RB 0
-#endif
-#ifndef DLSA_EVALCAT_NSLOT
-#define DLSA_EVALCAT_NSLOT 0
-#endif
 bool eval_cat_plan(EvalCatArgs& a) {
   const int BP = ec_bp(a.nbeta);
   const int fixed = ec_table_doubles(ec_entries(a), a.q, BP) * 8 + kEcStaticLds;
@@ -279,12 +272,9 @@ bool eval_cat_plan(EvalCatArgs& a) {
   for (int RB : {256, 128, 64}) {
     const int slot = ec_geom(RB, a.q, a.F).slot_bytes;
     if (fixed + 2 * slot > cap) continue;
-    if (DLSA_EVALCAT_RB && RB > DLSA_EVALCAT_RB) continue;
     a.rb = RB;
     int n = 2;
     while (n < 4 && fixed + (n + 1) * slot <= cap / 2) ++n;
-    if (DLSA_EVALCAT_NSLOT >= 2 && fixed + DLSA_EVALCAT_NSLOT * slot <= cap)
-      n = DLSA_EVALCAT_NSLOT;
     a.nslot = n;
     return true;
   }

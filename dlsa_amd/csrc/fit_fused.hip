@@ -5,12 +5,6 @@
 
 namespace dlsa {
 
-// the next iteration's approximate pass enqueued before the host reads the
-// counters (1) or after (0, A/B; FusedFit::spec_pass)
-#ifndef DLSA_SPEC_PASS
-#define DLSA_SPEC_PASS 1
-#endif
-
 namespace {
 
 struct ReadEvent {  // the counters' copy of an iteration (destroyed on every return)
@@ -179,7 +173,7 @@ hipError_t FusedFit::pass(int ph, const Plan& q, bool full, const std::vector<in
 }
 
 // The next iteration's approximate pass is enqueued before the host reads
-// this iteration's counters (DLSA_SPEC_PASS): a pass checks its partitions'
+// this iteration's counters: a pass checks its partitions'
 // phases on the device, so one enqueued for partitions that have since
 // switched or finished runs as a no-op, and the GPU no longer idles through
 // every hand-back (hipStreamSynchronize's return, the host's decisions and
@@ -278,7 +272,7 @@ int FusedFit::run() {
     DLSA_HIP_TRY(hipMemsetAsync(d_threc, 0, 8LL * K * P, stream));
   }
   ReadEvent read_ev;
-  if (DLSA_SPEC_PASS) DLSA_HIP_TRY(hipEventCreateWithFlags(&read_ev.ev, hipEventDisableTiming));
+  DLSA_HIP_TRY(hipEventCreateWithFlags(&read_ev.ev, hipEventDisableTiming));
 
   int it = 0;
   for (size_t lvl = 0; lvl < plans.size(); ++lvl) {
@@ -311,7 +305,7 @@ int FusedFit::run() {
       DLSA_HIP_TRY(enqueue_readback(sa, K, h, stream));
       // the next iteration's approximate pass, if this one had approximate
       // partitions and the next needs no first max |x| record (rec_x)
-      spec = DLSA_SPEC_PASS && n_running[PHASE_F32] > 0 && it + 1 < it_end &&
+      spec = n_running[PHASE_F32] > 0 && it + 1 < it_end &&
              !(use_oz && final_level && !colmax_ready);
       if (spec) {
         // wait for the copy only: the pass runs on while the host decides

@@ -417,10 +417,8 @@ inline int check_cat_shape(int q, int F, const int32_t* levels, int intercept, i
 }
 
 // level slots x replicas per factor of the numeric x dummy histograms before
-// the LDS budget shrinks them (A/B builds: DLSA_CAT_ND_CAP)
-#ifndef DLSA_CAT_ND_CAP
-#define DLSA_CAT_ND_CAP 256
-#endif
+// the LDS budget shrinks them
+constexpr int kCatNdCap = 256;
 // LDS layout of the categorical pass's histograms (cat_pass.hip): replicas so
 // that a frequent level does not serialise the lanes of a wave on one address
 // (nd: <= 128 slots per factor, pairs: <= 512 cells), shrunk until the
@@ -434,7 +432,7 @@ inline bool cat_layout(CatArgs& a, const int32_t* levels) {
   if (cat_exact_bucket(a))
     for (int f = 0; f < a.F; ++f)
       if (a.fold < 0 || levels[f] > levels[a.fold]) a.fold = f;
-  int nd_cap = DLSA_CAT_ND_CAP, pr_cap = 512;
+  int nd_cap = kCatNdCap, pr_cap = 512;
   for (int attempt = 0; attempt < 12; ++attempt) {
     int64_t o = 0;
     for (int f = 0; f < a.F; ++f) {

@@ -75,34 +75,6 @@ __device__ __forceinline__ void wait_vmcnt_le(int n) {
   }
 }
 
-// Workgroup barrier for the block loop: this wave's LDS reads/writes are
-// complete (lgkmcnt(0)), then s_barrier.  Unlike __syncthreads() it carries no
-// memory fence, whose lowering drains vmcnt to 0 -- that would wait for the
-// LDS-DMA of the blocks still streaming in, i.e. empty the ring at every
-// barrier.  The "memory" clobber keeps the compiler from moving LDS accesses
-// across it; the DMA'd slot of a block is waited for by each wave's counted
-// vmcnt before the first barrier that publishes it.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// Buffer resource with every word wave-uniform (readfirstlane): the LDS-DMA
-// loads then take it in SGPRs instead of a waterfall loop per load.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(uintptr_t base, uintptr_t bytes) {
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)base >> 32));
-  const uint32_t nr = __builtin_amdgcn_readfirstlane(
-      (uint32_t)(bytes < 0x7FFFFFF0u ? bytes : 0x7FFFFFF0u));
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), (short)0, (int)nr,
-                                           0x00020000);
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
 // Lane l and lane l ^ 16 (permlane16_swap), l and l ^ 32 (permlane32_swap):
 // both operands are v, so the swapped pair (x, y) holds the two halves and
 // x + y is the same sum, bitwise, in both lanes of the pair.

@@ -1,19 +1,17 @@
-// Ozaki-scheme exact pass: NT = 7 (see irls_oz.hip; NT = 8 would spill at 6
-// levels and keeps the fp64 pass).
+// Ozaki-scheme exact pass: NT = 7 (see irls_oz.hip; NT = 8 keeps the fp64
+// pass: its level accumulators do not fit the register file).
 #include "irls_oz_impl.hpp"
 
 namespace dlsa {
 
-hipError_t launch_irls_oz_g2(const PassArgs& a, int NT, bool std_, int family, int n_chunks,
-                             hipStream_t s) {
+hipError_t launch_irls_oz_g2(const PassArgs& a, int NT, bool std_, int n_chunks, hipStream_t s) {
   switch (NT) {
-    case 7: return launch_oz_nt<7>(a, std_, family, n_chunks, s);
+    case 7: return launch_oz_nt<7>(a, std_, n_chunks, s);
     default: return hipErrorInvalidValue;
   }
 }
 
 }  // namespace dlsa
-
 
 #ifdef DLSA_OZ_PROF
 // profiling build only: read and reset this unit's stamp sums (producer wave

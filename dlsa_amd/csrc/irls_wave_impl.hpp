@@ -50,19 +50,6 @@ __device__ __forceinline__ void wv_wait_vmcnt() {
   static_assert(N >= 0 && N < 64, "vmcnt is 6 bits on gfx950");
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
-// wait until at most n (runtime, <= N) vector-memory ops of this wave are
-// outstanding
-template <int N>
-__device__ __forceinline__ void wv_wait_vmcnt_le(int n) {
-  if constexpr (N <= 0) {
-    wv_wait_vmcnt<0>();
-  } else {
-    if (n >= N)
-      wv_wait_vmcnt<N>();
-    else
-      wv_wait_vmcnt_le<N - 1>(n);
-  }
-}
 
 __device__ __forceinline__ double wv_xor16(double v) {
   const unsigned lo = __double2loint(v), hi = __double2hiint(v);
@@ -85,12 +72,6 @@ __device__ __forceinline__ double wv_swap32(double v, bool upper) {
   const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
   return upper ? __hiloint2double(b[0], a[0]) : __hiloint2double(b[1], a[1]);
 }
-template <int CTRL>
-__device__ __forceinline__ double wv_dpp(double v) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
 
 // Sum over the LPR lanes of one row (lanes l, l + R, l + 2R, ...); every lane
 // of the row ends with the bitwise-identical total (each step adds a
@@ -99,22 +80,10 @@ template <int R>
 __device__ __forceinline__ double wv_row_sum(double v) {
   static_assert(R == 16 || R == 8 || R == 4, "16, 8 or 4 rows per block");
   if constexpr (R == 4) v += __shfl_xor(v, 4);   // l ^ 4 (no DPP form)
-  if constexpr (R <= 8) v += wv_dpp<0x128>(v);  // row_ror 8: l ^ 8
+  if constexpr (R <= 8) v += dpp_f64<0x128>(v);  // row_ror 8: l ^ 8
   v = wv_xor16(v);
   v = wv_xor32(v);
   return v;
-}
-
-// Buffer resource with every word made wave-uniform (readfirstlane), so the
-// LDS-DMA loads take it in SGPRs: without this the compiler may keep it in
-// VGPRs and wrap every buffer_load ... lds in a waterfall loop.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wv_rsrc(uintptr_t base, uintptr_t bytes) {
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)base >> 32));
-  const uint32_t nr = __builtin_amdgcn_readfirstlane(
-      (uint32_t)(bytes < 0x7FFFFFF0u ? bytes : 0x7FFFFFF0u));
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), (short)0, (int)nr,
-                                           0x00020000);
 }
 
 // 1 / d for d in [1, 3]: hardware estimate + two Newton steps (~1 ulp; the
@@ -153,26 +122,11 @@ __device__ __forceinline__ double wv_log12(double t) {
 
 }  // namespace
 
-// Ring slots per workgroup (DLSA_WAVE_NSLOT, DLSA_WAVE_NSLOT_OLS): 2 = one
-// block in flight while the current one is computed; 3 = two blocks in
-// flight.  Three slots for the OLS pass (8-row, 4 KiB blocks at P = 64) measured
-// slower (config-4 pass 16.7-17.1 vs 14.9-15.2 ms, profiles/r04h_ols_ab.txt).
-#ifndef DLSA_WAVE_NSLOT
-#define DLSA_WAVE_NSLOT 2
-#endif
-#ifndef DLSA_WAVE_NSLOT_OLS
-#define DLSA_WAVE_NSLOT_OLS 2
-#endif
-__host__ __device__ constexpr int wave_slots(int FAM) {
-  return FAM == FAMILY_GAUSSIAN ? DLSA_WAVE_NSLOT_OLS : DLSA_WAVE_NSLOT;
-}
-// OLS without standardisation: a full block's row phase writes nothing the
-// other wave reads (w = 1 is a constant of the tile phase), so the barrier
-// between the row and tile phases can be kept for the tail block only
-// (DLSA_WAVE_OLS_ONESYNC = 1; not faster: 15.2 vs 14.9-15.0 ms, r04h)
-#ifndef DLSA_WAVE_OLS_ONESYNC
-#define DLSA_WAVE_OLS_ONESYNC 0
-#endif
+// Ring slots per workgroup: one block in flight while the current one is
+// computed.  Three slots (two blocks in flight) for the OLS pass (8-row, 4 KiB
+// blocks at P = 64) measured slower (config-4 pass 16.7-17.1 vs 14.9-15.2 ms,
+// profiles/r04h_ols_ab.txt).
+constexpr int kWaveSlots = 2;
 // Ring slot: [16 B pad][npieces KiB of X rows][256 B: y of up to 32 rows]
 __host__ __device__ __forceinline__ int wave_npieces(int RB, int p) {
   return (RB * p * 8 + 16 + 1023) / 1024;
@@ -182,8 +136,8 @@ __host__ __device__ __forceinline__ int wave_slot_bytes_impl(int RB, int p) {
 }
 // LDS of one workgroup: 2 ring slots + w of a block [RB] + theta [PMAX] +
 // center / 1/scale [2][PMAX]
-__host__ __device__ __forceinline__ int wave_lds_bytes_impl(int NT, int RB, int p, int FAM) {
-  return wave_slots(FAM) * wave_slot_bytes_impl(RB, p) + RB * 8 + 3 * 16 * NT * 8;
+__host__ __device__ __forceinline__ int wave_lds_bytes_impl(int NT, int RB, int p) {
+  return kWaveSlots * wave_slot_bytes_impl(RB, p) + RB * 8 + 3 * 16 * NT * 8;
 }
 
 // Waves per workgroup.  W = 2 (P <= 112): the T tiles are split over two
@@ -191,7 +145,7 @@ __host__ __device__ __forceinline__ int wave_lds_bytes_impl(int NT, int RB, int 
 // so two workgroups' waves share every SIMD and one wave's LDS / DMA /
 // dependency waits are covered by the other's MFMAs; the rows of a block are
 // split between the waves in the row phase (P >= 17).  W = 1 (P <= 128): all T tiles
-// in one wave, one wave per SIMD.  DLSA_WAVE_W overrides for profiling.
+// in one wave, one wave per SIMD.
 constexpr int wave_w_default(int NT) { return (NT >= 2 && NT <= 7) ? 2 : 1; }
 // Lanes per row in the row phase: 4 (16 rows per wave) at W = 1, P <= 112; 16 (4
 // rows per wave, 8-row blocks) for OLS at W = 2, P <= 64; else 8.  The OLS
@@ -206,7 +160,7 @@ constexpr int wave_lpr(int NT, int W, int FAM) {
 }
 constexpr int wave_rb(int NT, int W, int FAM) { return W * (64 / wave_lpr(NT, W, FAM)); }
 
-// Edge strip (DLSA_WAVE_STRIP, default on).  The last tile row holds only
+// Edge strip.  The last tile row holds only
 // s = P - 16 (NT - 1) parameter rows (4 at P = 100).  On the MI355X a
 // v_mfma_f64_4x4x4_4b issues every ~7 ns per SIMD (75 TF/s chip-wide;
 // tools/mfma4_probe.hip, profiles/r02_mfma4_probe.txt) -- a quarter of a
@@ -224,14 +178,8 @@ constexpr int wave_rb(int NT, int W, int FAM) { return W * (64 / wave_lpr(NT, W,
 // OLS: the tile phase takes x itself as the A operand (no w * x multiplies;
 // padded rows are zeroed in the ring by the row phase): 16.2-16.4 vs
 // 16.4-16.5 ms per config-4 pass (profiles/r02av_ols_nomul_ab.txt)
-#ifndef DLSA_WAVE_OLS_NOMUL
-#define DLSA_WAVE_OLS_NOMUL 1
-#endif
-#ifndef DLSA_WAVE_STRIP
-#define DLSA_WAVE_STRIP 1
-#endif
 constexpr int wave_strip_ns(int NT, int P) {
-  return (!DLSA_WAVE_STRIP || NT < 2) ? 0
+  return (NT < 2)                     ? 0
          : (P - 16 * (NT - 1) <= 4)   ? 1
          : (P - 16 * (NT - 1) <= 8)   ? 2
                                       : 0;
@@ -303,37 +251,6 @@ struct WaveTiles {
   }
 };
 
-// MFMA issue order of a wave's tiles (DLSA_WAVE_ORDER = 1): greedy, each
-// next tile taking a different A operand (tile row) AND a different B operand
-// (tile column) than the previous one where one is left -- back-to-back fp64
-// MFMAs on a shared operand register issue slower (tools/mfma_rate_probe.hip).
-// 0: tiles in row order (the rows' A operand reused back to back).
-#ifndef DLSA_WAVE_ORDER
-#define DLSA_WAVE_ORDER 0
-#endif
-template <class TL, int TW>
-struct WaveIssueOrder {
-  static constexpr std::array<int, TW> make() {
-    std::array<int, TW> ord{};
-    bool used[TW > 0 ? TW : 1] = {};
-    int pi = -1, pj = -1;
-    for (int n = 0; n < TW; ++n) {
-      int pick = -1;
-      if (DLSA_WAVE_ORDER)
-        for (int i = 0; i < TW && pick < 0; ++i)
-          if (!used[i] && TL::I_of(i) != pi && TL::J_of(i) != pj) pick = i;
-      for (int i = 0; i < TW && pick < 0; ++i)
-        if (!used[i]) pick = i;
-      used[pick] = true;
-      ord[n] = pick;
-      pi = TL::I_of(pick);
-      pj = TL::J_of(pick);
-    }
-    return ord;
-  }
-  static constexpr std::array<int, TW> ord = make();
-};
-
 template <typename F, int... Is>
 __device__ __forceinline__ void wv_static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
   (f(std::integral_constant<int, Is>{}), ...);
@@ -345,11 +262,11 @@ __device__ __forceinline__ void wv_static_for(F&& f) {
 
 // workgroup sync of the block loop: this wave's LDS ops done, then (W > 1) a
 // barrier without the vmcnt drain of __syncthreads (the next block's DMA
-// stays in flight; irls_coop_impl.hpp lds_barrier)
+// stays in flight; lds_barrier)
 template <int W>
 __device__ __forceinline__ void wv_sync() {
   if constexpr (W > 1)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
   else
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
@@ -379,14 +296,12 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
   constexpr int TW = TL::TW, NC = TL::NC;
   // OLS (w in {0, 1}): A operands are x itself (padded rows zeroed in the ring,
   // the intercept column = w)
-  constexpr bool OLS_NOMUL = DLSA_WAVE_OLS_NOMUL && FAM == FAMILY_GAUSSIAN;
+  constexpr bool OLS_NOMUL = FAM == FAMILY_GAUSSIAN;
   // OLS is one pass at theta = 0 (fit_dense: fit_init zeroes theta, max_iter =
   // 1, no warm-start levels, no polish): eta = 0 and r = y, so the row phase
   // skips the x . theta dot products and their row reductions -- fp64 VALU
   // work that never co-executes with the fp64 MFMAs of the tile phase
   constexpr bool ETA0 = FAM == FAMILY_GAUSSIAN;
-  constexpr int kWaveSlots = wave_slots(FAM);
-  constexpr bool ONESYNC = DLSA_WAVE_OLS_ONESYNC && OLS_NOMUL && !STD;
 
   const int lane = threadIdx.x & 63;
   const int p = a.p, P = a.P, ic = a.intercept;
@@ -412,9 +327,6 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
   }
 
   // DMA: wave WID issues pieces j = WID, WID + W, ...; the last wave also y
-  int my_ops = 0;
-  for (int j = WID; j < cx.npieces; j += W) ++my_ops;
-  if (WID == W - 1) ++my_ops;
   auto issue = [&](int blk) {
     char* sbase = smem + (blk % kWaveSlots) * cx.slot_bytes;
     const uintptr_t start = (uintptr_t)(a.X + (cx.row0 + (int64_t)blk * RB) * p);
@@ -431,13 +343,8 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
   const bool icpt_lane = ic && fl == 0;
   for (int b = 0; b < kWaveSlots - 1 && b < cx.nb; ++b) issue(b);
   for (int b = 0; b < cx.nb; ++b) {
-    // this wave's pieces of block b landed (the younger blocks' may not have)
-    if constexpr (kWaveSlots == 2) {
-      wv_wait_vmcnt<0>();
-    } else {
-      const int younger = min(kWaveSlots - 2, cx.nb - 1 - b);  // blocks issued after b
-      wv_wait_vmcnt_le<2 * 8>(younger * my_ops);
-    }
+    static_assert(kWaveSlots == 2, "one block in flight: the wait is for all of this wave's DMA");
+    wv_wait_vmcnt<0>();  // this wave's pieces of block b landed
     wv_sync<W>();        // every wave's pieces landed; block b-1 fully consumed
     if (b + kWaveSlots - 1 < cx.nb) issue(b + kWaveSlots - 1);  // into the slot of block b-1
     const char* slot = smem + (b % kWaveSlots) * cx.slot_bytes;
@@ -501,11 +408,10 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
       for (int m = 0; m < M; ++m) gacc[m] = fma(xv[m], r, gacc[m]);
       if (sl == 0) wv[row] = w;
     }
-    // w (and standardised / zeroed x) of all rows visible
-    if constexpr (W > 1) {
-      if (!ONESYNC || rows_left < RB) wv_sync<W>();  // workgroup-uniform
-    }
-    const bool w_one = ONESYNC && rows_left >= RB;  // full OLS block: w = 1 on every row
+    // w (and standardised / zeroed x) of all rows visible.  (OLS without
+    // standardisation could skip this barrier on full blocks, where w = 1; it
+    // measured not faster: 15.2 vs 14.9-15.0 ms, profiles/r04h_ols_ab.txt)
+    if constexpr (W > 1) wv_sync<W>();
 
     // ---- tile phase: KS k-steps of 4 rows, this wave's TW tiles ---------------
     // operands of k-step s+1 are read while the MFMAs of k-step s run
@@ -520,7 +426,7 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
 #pragma unroll
         for (int r = 0; r < NS; ++r) xso[u][r] = xt[4 * r];
       }
-      wk[u] = w_one ? 1.0 : wv[4 * s + q];
+      wk[u] = wv[4 * s + q];
     };
     load(0, 0);
 #pragma unroll
@@ -540,8 +446,9 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
 #pragma unroll
         for (int r = 0; r < NS; ++r) as[r] = OLS_NOMUL ? xso[u][r] : xso[u][r] * wk[u];
       }
-      wv_static_for<TW>([&](auto oI) {
-        constexpr int i = WaveIssueOrder<TL, TW>::ord[decltype(oI)::value];
+      // tiles in row order: a row's A operand is reused back to back
+      wv_static_for<TW>([&](auto iI) {
+        constexpr int i = decltype(iI)::value;
         constexpr int I = TL::I_of(i), J = TL::J_of(i);
         if constexpr (strip(I)) {
 #pragma unroll
@@ -637,7 +544,6 @@ __global__ __launch_bounds__(64 * W, wave_min_waves(NT, W, FAM)) void irls_wave_
   cx.nrows = __builtin_amdgcn_readfirstlane(a.chunk_rows[cx.chunk]);
   cx.nb = (cx.nrows + RB - 1) / RB;
   cx.npieces = wave_npieces(RB, p);
-  constexpr int kWaveSlots = wave_slots(FAM);
   cx.slot_bytes = wave_slot_bytes_impl(RB, p);
   cx.slot_y = 16 + cx.npieces * 1024;
   double* wv = (double*)(smem + kWaveSlots * cx.slot_bytes);
@@ -661,9 +567,9 @@ __global__ __launch_bounds__(64 * W, wave_min_waves(NT, W, FAM)) void irls_wave_
   __syncthreads();
 
   cx.xcb = (uintptr_t)(a.X + cx.row0 * p) & ~(uintptr_t)15;
-  cx.xr = wv_rsrc(cx.xcb, a.x_last16 + 16 - cx.xcb);
+  cx.xr = uniform_rsrc(cx.xcb, a.x_last16 + 16 - cx.xcb);
   const uintptr_t ycb = (uintptr_t)(a.y + cx.row0);
-  cx.yr = wv_rsrc(ycb, a.y_last4 + 4 - ycb);
+  cx.yr = uniform_rsrc(ycb, a.y_last4 + 4 - ycb);
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   if constexpr (W == 1) {
     wave_body<NT, NS, 1, 0, STD, FAM>(a, cx, smem);
@@ -684,7 +590,7 @@ static inline int wave_w(int NT, int requested = 0) {
 
 template <int NT, int W, bool STD, int FAM>
 static hipError_t launch_wave_t(const PassArgs& a, int n_chunks, hipStream_t s) {
-  const size_t lds = wave_lds_bytes_impl(NT, wave_rb(NT, W, FAM), a.p, FAM);
+  const size_t lds = wave_lds_bytes_impl(NT, wave_rb(NT, W, FAM), a.p);
   switch (wave_strip_ns(NT, a.P)) {
     case 1:
       hipLaunchKernelGGL((irls_wave_kernel<NT, 1, W, STD, FAM>), dim3(n_chunks), dim3(64 * W), lds,

@@ -20,20 +20,6 @@
 // write them (newton_solve.hip sums a partition's chunks in fixed order).
 #include "dlsa_internal.hpp"
 
-// OLS pass by this kernel (1) or by the per-wave LDS-DMA kernel (0, A/B)
-#ifndef DLSA_OLS_STREAM
-#define DLSA_OLS_STREAM 1
-#endif
-// each k-step group loaded then computed (0), or the next group's loads in
-// flight under the current group's MFMAs in a second register set (1, A/B).
-// Round 6, config 4, alternated: two sets measured 12.08-12.44 ms per pass at
-// KS = 2 / 3 / 4 and 12.7 at 6, one set (KS = 8) 12.06-12.11
-// (profiles/r06q_ols_prefetch_ab.txt): with 2-3 waves per SIMD the loads of
-// one wave already run under the other waves' MFMAs
-#ifndef DLSA_OLS_PF
-#define DLSA_OLS_PF 0
-#endif
-
 namespace dlsa {
 
 namespace {
@@ -151,28 +137,16 @@ __global__ __launch_bounds__(64 * kOlsWaves) void ols_stream_kernel(const PassAr
     }
   };
   constexpr int GR = 4 * KS;  // rows per group
-#if DLSA_OLS_PF
-  // two register sets: the next group's loads are in flight while the
-  // current group's MFMAs run (the loop is unrolled by two, so no register
-  // copies cross the back edge; no early exit, which made the compiler keep a
-  // second set of accumulators).  A group past the chunk loads 0 from the
-  // bounds-checked buffers and adds zeros (masked when not FULL), in the
-  // single-set loop's accumulation order
-  double xa[KS][NT], ya[KS], xb[KS][NT], yb[KS];
-  load_group(0, xa, ya);
-  for (int r0 = 0; r0 < nrows; r0 += 2 * GR) {
-    load_group(r0 + GR, xb, yb);
-    compute_group(r0, xa, ya);
-    load_group(r0 + 2 * GR, xa, ya);
-    compute_group(r0 + GR, xb, yb);
-  }
-#else
+  // each group loaded, then computed: with 2-3 waves per SIMD the loads of one
+  // wave already run under the other waves' MFMAs (a second register set with
+  // the next group's loads in flight measured 12.08-12.44 ms per config-4 pass
+  // at KS = 2 / 3 / 4 and 12.7 at 6, against 12.06-12.11 for this loop at
+  // KS = 8, profiles/r06q_ols_prefetch_ab.txt)
   for (int r0 = 0; r0 < nrows; r0 += GR) {
     double xv[KS][NT], yv[KS];
     load_group(r0, xv, yv);
     compute_group(r0, xv, yv);
   }
-#endif
 
   // ---- epilogue: the chunk's slab (f64 16x16x4 C/D map: row q + 4 r, column fl)
   double* sH = a.slab_H + (int64_t)chunk * T * 256;
@@ -196,13 +170,11 @@ __global__ __launch_bounds__(64 * kOlsWaves) void ols_stream_kernel(const PassAr
 // 4), 8 (2 waves per SIMD, 32 rows of loads in flight per wave) measured
 // 11.96-12.26 ms per pass against 12.18-12.34 for 4 (3 waves per SIMD),
 // 12.25-12.31 for 12 and 12.3-12.6 for 2 (4 waves per SIMD); 16 measured
-// 13.5 ms (profiles/r05ok_ols_ks_sweep.jsonl).  DLSA_OLS_KS: A/B builds.
-#ifndef DLSA_OLS_KS
-#define DLSA_OLS_KS 8
-#endif
+// 13.5 ms (profiles/r05ok_ols_ks_sweep.jsonl).
+constexpr int kOlsKS = 8;
 template <int NT>
 hipError_t launch_ols_nt(const PassArgs& a, bool standardize, int n_chunks, hipStream_t s) {
-  constexpr int KS = DLSA_OLS_KS;
+  constexpr int KS = kOlsKS;
   const dim3 grid((n_chunks + kOlsWaves - 1) / kOlsWaves), block(64 * kOlsWaves);
   const bool full = a.intercept == 0 && a.p == 16 * NT;
   if (standardize) {
@@ -221,7 +193,7 @@ hipError_t launch_ols_nt(const PassArgs& a, bool standardize, int n_chunks, hipS
 
 }  // namespace
 
-bool ols_stream_applies(int NT) { return DLSA_OLS_STREAM && NT >= 1 && NT <= 4; }
+bool ols_stream_applies(int NT) { return NT >= 1 && NT <= 4; }
 
 hipError_t launch_ols_stream(const PassArgs& a, int NT, bool standardize, int n_chunks,
                              hipStream_t s) {

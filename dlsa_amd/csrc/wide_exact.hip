@@ -7,11 +7,6 @@
 #include "irls_wave_impl.hpp"  // wv_* wave helpers
 #include "wide_common.hpp"
 
-// rows per wave and step of the wide row pass (A/B builds)
-#ifndef DLSA_WIDE_ROW_U
-#define DLSA_WIDE_ROW_U 4
-#endif
-
 namespace dlsa {
 
 // ---------------------------------------------------------------------------
@@ -56,7 +51,7 @@ __global__ __launch_bounds__(256) void wide_row_kernel(const WideArgs a) {
   uint32_t zmx[MB];
 #pragma unroll
   for (int m = 0; m < MB; ++m) zmx[m] = 0u;
-  constexpr int U = DLSA_WIDE_ROW_U;  // rows per wave per step (all U rows' loads in flight)
+  constexpr int U = 4;  // rows per wave per step (all U rows' loads in flight)
   for (int base = wid * U; base < nrows; base += 4 * U) {
     double xv[U][MB], yv[U];
 #pragma unroll
@@ -190,8 +185,8 @@ __global__ __launch_bounds__(256, 2) void wide_gram_kernel(const WideArgs a) {
     }
   }
   const __amdgpu_buffer_rsrc_t xr =
-      wv_rsrc((uintptr_t)(a.X + row0 * p), (uintptr_t)nrows * (uintptr_t)p * 8u);
-  const __amdgpu_buffer_rsrc_t wr = wv_rsrc((uintptr_t)(a.w + row0), (uintptr_t)nrows * 8u);
+      uniform_rsrc((uintptr_t)(a.X + row0 * p), (uintptr_t)nrows * (uintptr_t)p * 8u);
+  const __amdgpu_buffer_rsrc_t wr = uniform_rsrc((uintptr_t)(a.w + row0), (uintptr_t)nrows * 8u);
 
   d4w acc[4][4];
 #pragma unroll

@@ -80,10 +80,10 @@ __host__ __device__ constexpr int fused_lds_bytes(int NT16) {
 // (each step adds a value and its partner's under a lane involution, so the
 // pair computes a + b and b + a).
 __device__ __forceinline__ double wave_allsum(double v) {
-  v += wv_dpp<0x141>(v);  // row_half_mirror: i <-> 7 - i
-  v += wv_dpp<0xB1>(v);   // quad_perm [1, 0, 3, 2]
-  v += wv_dpp<0x4E>(v);   // quad_perm [2, 3, 0, 1]
-  v += wv_dpp<0x140>(v);  // row_mirror: i <-> 15 - i
+  v += dpp_f64<0x141>(v);  // row_half_mirror: i <-> 7 - i
+  v += dpp_f64<0xB1>(v);   // quad_perm [1, 0, 3, 2]
+  v += dpp_f64<0x4E>(v);   // quad_perm [2, 3, 0, 1]
+  v += dpp_f64<0x140>(v);  // row_mirror: i <-> 15 - i
   v = wv_xor16(v);
   v = wv_xor32(v);
   return v;
@@ -115,10 +115,10 @@ __device__ __forceinline__ double reduce_scatter4(const double (&v)[4], int lane
   const double s0 = swap_add<32>(v[0], v[2]), s1 = swap_add<32>(v[1], v[3]);
   // 16-lane groups: rows 0, 1, 2, 3
   double r = swap_add<16>(s0, s1);
-  r += wv_dpp<0x141>(r);  // row_half_mirror: i <-> 7 - i
-  r += wv_dpp<0xB1>(r);   // quad_perm [1, 0, 3, 2]
-  r += wv_dpp<0x4E>(r);   // quad_perm [2, 3, 0, 1]
-  r += wv_dpp<0x140>(r);  // row_mirror: i <-> 15 - i
+  r += dpp_f64<0x141>(r);  // row_half_mirror: i <-> 7 - i
+  r += dpp_f64<0xB1>(r);   // quad_perm [1, 0, 3, 2]
+  r += dpp_f64<0x4E>(r);   // quad_perm [2, 3, 0, 1]
+  r += dpp_f64<0x140>(r);  // row_mirror: i <-> 15 - i
   return r;
 }
 
@@ -133,10 +133,10 @@ __device__ __forceinline__ double reduce_scatter8(const double (&v)[8], int lane
   // 8-lane groups: lanes with bit 3 clear keep t0's row, set keep t1's
   const bool b3 = (lane & 8) != 0;
   const double keep = b3 ? t1 : t0, give = b3 ? t0 : t1;
-  double r = keep + wv_dpp<0x128>(give);  // row_ror 8: lane l ^ 8 within 16
-  r += wv_dpp<0x141>(r);                  // row_half_mirror: i <-> 7 - i
-  r += wv_dpp<0xB1>(r);                   // quad_perm [1, 0, 3, 2]
-  r += wv_dpp<0x4E>(r);                   // quad_perm [2, 3, 0, 1]
+  double r = keep + dpp_f64<0x128>(give);  // row_ror 8: lane l ^ 8 within 16
+  r += dpp_f64<0x141>(r);                  // row_half_mirror: i <-> 7 - i
+  r += dpp_f64<0xB1>(r);                   // quad_perm [1, 0, 3, 2]
+  r += dpp_f64<0x4E>(r);                   // quad_perm [2, 3, 0, 1]
   return r;
 }
 
@@ -237,8 +237,8 @@ __global__ __launch_bounds__(64 * FW, 1) void wide_fused_bf16_kernel(const WideA
 #endif
     const int rows = max(0, min(32, nrows - 32 * b));
     const __amdgpu_buffer_rsrc_t xr =
-        wv_rsrc((uintptr_t)(a.X + rb * p), (uintptr_t)rows * (uintptr_t)p * 8u);
-    const __amdgpu_buffer_rsrc_t yr = wv_rsrc((uintptr_t)(a.y + rb), (uintptr_t)rows * 8u);
+        uniform_rsrc((uintptr_t)(a.X + rb * p), (uintptr_t)rows * (uintptr_t)p * 8u);
+    const __amdgpu_buffer_rsrc_t yr = uniform_rsrc((uintptr_t)(a.y + rb), (uintptr_t)rows * 8u);
 #pragma unroll
     for (int u = 4 * h; u < 4 * h + 4; ++u) {
       const int so = u * p * 8;
@@ -359,7 +359,7 @@ __global__ __launch_bounds__(64 * FW, 1) void wide_fused_bf16_kernel(const WideA
       issue(b + 1, h);
     }
     // this wave's Z writes done; every wave's image b complete and image b-1 consumed
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
 
     // ---- MFMA phase: per pair q, tile rows NT16 - 1 - q (J < nh) and q ------
     // operand (feature 16 J + fl, rows 8 kg .. 8 kg + 7): planes 2 kg, 2 kg + 1

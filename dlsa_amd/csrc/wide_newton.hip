@@ -8,12 +8,6 @@
 #include "newton_step.hpp"
 #include "wide_common.hpp"
 
-// wide Newton: the trailing update of the approximate iterations on the f32
-// MFMA (1) or on the fp64 MFMA like the exact ones (0, A/B)
-#ifndef DLSA_WN_F32
-#define DLSA_WN_F32 1
-#endif
-
 // Profiling build (DLSA_WN_PROF, tools/build_variants.sh wnprof): cycle stamps
 // of the wide Newton kernel's stages, summed over workgroup runs into
 // g_wn_prof (one vector atomic per stage per run; wave 1 stamps its share of
@@ -38,10 +32,7 @@ constexpr int CB = 32;         // Cholesky panel width
 // on banks 4 fl + 2 kq (+1), all 64 distinct; CB + 1 put (fl, kq = 1) and
 // (fl + 1, kq = 0) on one bank pair (2-way).  The row-per-thread reads of the
 // panel solve take the 2-way instead (16x fewer instructions).
-#ifndef DLSA_WN_LDP
-#define DLSA_WN_LDP (CB + 2)
-#endif
-constexpr int LDP = DLSA_WN_LDP;
+constexpr int LDP = CB + 2;
 static_assert(LDP > CB, "the padding slot CB holds the reciprocal pivots");
 static_assert((CB * LDP + DLSA_MAX_P * LDP + 2 * DLSA_MAX_P + 64) * 8 <= 160 * 1024,
               "wide_newton_kernel LDS at PP = DLSA_MAX_P");
@@ -235,7 +226,7 @@ __global__ __launch_bounds__(1024) void wide_newton_kernel(const SolveArgs a, co
   // two forms' C/D maps differ: lane (kq, fl), register r holds row kq + 4 r
   // (fp64) or 4 kq + r (f32) of column fl, so C is read and written in the
   // map of the form in use.
-  const bool lowp = phase == PHASE_F32 && DLSA_WN_F32;
+  const bool lowp = phase == PHASE_F32;
   const int crow = lowp ? 4 * kq : kq, cstep = lowp ? 1 : 4;
   auto trail = [&](int jb, int m, bool cols01, int w0, int nw) {
     const int ntiles = cols01 ? 2 * m - 1 : (m - 2) * (m - 1) / 2;

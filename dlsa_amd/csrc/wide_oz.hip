@@ -162,7 +162,7 @@ __global__ __launch_bounds__(512, 1) void wide_oz_gram_kernel(const WideArgs a, 
   // 5 KB of features 128 I .. 128 I + 127 (A) / 128 J .. (B) of its 3 slices
   const uintptr_t gbase = (uintptr_t)(o.D + (int64_t)g * o.maxblk * 4 * PP * kRec);
   const __amdgpu_buffer_rsrc_t dr =
-      wv_rsrc(gbase, (uintptr_t)o.maxblk * 4 * PP * kRec);
+      uniform_rsrc(gbase, (uintptr_t)o.maxblk * 4 * PP * kRec);
   const int stepb = 4 * PP * kRec;
   // this wave's DMA pieces of a step: 40 x 1 KB (A: 20, B: 20), 5 per wave;
   // a rowblock's panel is 5 KB: slices 0 and 1 (2 KB each), slice 2 (1 KB)
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(512, 1) void wide_oz_gram_kernel(const WideArgs a, 
     wv_wait_vmcnt<5>();
   else
     wv_wait_vmcnt<0>();
-  ozk::barrier();
+  lds_barrier();
   for (int s = 0; s < nsteps; ++s) {
     if (s + 2 < nsteps) issue(s + 2);
     if (!idle) {
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(512, 1) void wide_oz_gram_kernel(const WideArgs a, 
       wv_wait_vmcnt<5>();
     else
       wv_wait_vmcnt<0>();
-    ozk::barrier();  // (not __syncthreads: its fence would drain step s+2's DMA)
+    lds_barrier();  // (not __syncthreads: its fence would drain step s+2's DMA)
   }
   if (idle) return;
   // C/D map of the i32 16x16 MFMA: row 4 (l >> 4) + r, column l & 15
