@@ -90,6 +90,12 @@ SIGNATURES = {
         ctypes.c_int,
         [_P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _F64, _P, _P, _P, _P, _P, _P,
          ctypes.POINTER(FitOptions), _P]),
+    "dlsa_poisson_fit_batched_ex": (
+        ctypes.c_int,
+        [_P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _F64, _P, _P, _P, _P, _P, _P,
+         ctypes.POINTER(FitOptions), _P]),
+    "dlsa_poisson_loglik_batched_sum": (
+        ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
     "dlsa_ols_fit_batched": (
         ctypes.c_int,
         [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(FitOptions),

@@ -37,15 +37,18 @@ hipError_t launch_fit_init(const int64_t* offsets_dev, int K, int P, int start_p
 // Start of a warm-start level: running partitions re-enter the Newton loop
 // (the log-likelihood scale changes with the row count), non-finite iterates
 // restart from 0; counters[phase] = partitions running.
+// theta0 (Poisson, else null): the restart value of parameter 0.
 __global__ void level_reset_kernel(int K, int P, int start_phase, int32_t* phase,
                                    int32_t* status, double* ll_prev, int32_t* backtracks,
-                                   double* theta, int32_t* counters) {
+                                   double* theta, int32_t* counters, const double* theta0) {
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < K; k += gridDim.x * blockDim.x) {
     if (status[k] != STATUS_RUNNING) continue;
     bool finite = true;
     for (int f = 0; f < P; ++f) finite &= (bool)isfinite(theta[(int64_t)k * P + f]);
-    if (!finite)
+    if (!finite) {
       for (int f = 0; f < P; ++f) theta[(int64_t)k * P + f] = 0.0;
+      if (theta0) theta[(int64_t)k * P] = theta0[k];
+    }
     phase[k] = start_phase;
     ll_prev[k] = -INFINITY;
     backtracks[k] = 0;
@@ -55,9 +58,76 @@ __global__ void level_reset_kernel(int K, int P, int start_phase, int32_t* phase
 
 hipError_t launch_level_reset(int K, int P, int start_phase, int32_t* phase, int32_t* status,
                               double* ll_prev, int32_t* backtracks, double* theta,
-                              int32_t* counters, hipStream_t s) {
+                              int32_t* counters, hipStream_t s, const double* theta0) {
   hipLaunchKernelGGL(level_reset_kernel, dim3((K + 255) / 256), dim3(256), 0, s, K, P,
-                     start_phase, phase, status, ll_prev, backtracks, theta, counters);
+                     start_phase, phase, status, ll_prev, backtracks, theta, counters, theta0);
+  return hipGetLastError();
+}
+
+// Poisson start point, after fit_init: one workgroup per partition sums y in a
+// fixed order (thread t takes rows t, t + 256, ...; xor butterfly inside the
+// wave, then the four waves in index order: the same bits run to run) and
+// takes min y and a finiteness flag along.  With an intercept the fit starts
+// at the MLE of the intercept-only model, theta = (log mean y, 0, ..., 0):
+// from theta = 0 a Newton step at mean y ~ 50 overshoots to eta ~ 50.
+// Without an intercept the start stays theta = 0.  theta0[k] keeps the start
+// value of parameter 0 for the restarts (level_fail, level_reset_kernel).
+// A partition with a negative or non-finite y ends NONFINITE, one with
+// sum y = 0 (its MLE does not exist) SINGULAR, both before any pass and with
+// the zeroed outputs fit_init wrote.
+__global__ __launch_bounds__(256) void poisson_start_kernel(const double* y, const int64_t* offsets,
+                                                            int P, int intercept, double* theta,
+                                                            double* theta0, int32_t* phase,
+                                                            int32_t* status) {
+  __shared__ double ssum[4], smin[4];
+  __shared__ int sbad[4];
+  const int k = blockIdx.x;
+  const int64_t r0 = offsets[k], r1 = offsets[k + 1];
+  double sum = 0.0, mn = INFINITY;
+  int bad = 0;
+  for (int64_t i = r0 + threadIdx.x; i < r1; i += 256) {
+    const double v = y[i];
+    bad |= !isfinite(v);
+    sum += v;
+    mn = fmin(mn, v);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sum += __shfl_xor(sum, o);
+    mn = fmin(mn, __shfl_xor(mn, o));
+    bad |= __shfl_xor(bad, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    ssum[threadIdx.x >> 6] = sum;
+    smin[threadIdx.x >> 6] = mn;
+    sbad[threadIdx.x >> 6] = bad;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  sum = ((ssum[0] + ssum[1]) + ssum[2]) + ssum[3];
+  mn = fmin(fmin(smin[0], smin[1]), fmin(smin[2], smin[3]));
+  bad = sbad[0] | sbad[1] | sbad[2] | sbad[3];
+  theta0[k] = 0.0;
+  if (r1 <= r0) return;  // empty: fit_init's DLSA_STATUS_EMPTY stands
+  if (bad || !(mn >= 0.0) || !isfinite(sum)) {
+    status[k] = DLSA_STATUS_NONFINITE;
+    phase[k] = PHASE_DONE;
+  } else if (!(sum > 0.0)) {
+    status[k] = DLSA_STATUS_SINGULAR;
+    phase[k] = PHASE_DONE;
+  } else if (intercept) {
+    const double t0 = log(sum / (double)(r1 - r0));
+    theta0[k] = t0;
+    theta[(int64_t)k * P] = t0;
+  }
+}
+
+hipError_t launch_poisson_start(const double* y, const int64_t* offsets_dev, int K, int P,
+                                int intercept, double* theta, double* theta0, int32_t* phase,
+                                int32_t* status, hipStream_t s) {
+  if (K <= 0) return hipSuccess;
+  hipLaunchKernelGGL(poisson_start_kernel, dim3(K), dim3(256), 0, s, y, offsets_dev, P, intercept,
+                     theta, theta0, phase, status);
   return hipGetLastError();
 }
 

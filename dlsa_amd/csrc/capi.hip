@@ -46,6 +46,11 @@ static int fit_dense(int family, const double* X, const double* y, const int64_t
     set_error("P = p + intercept > " + std::to_string(DLSA_MAX_P) + " is not supported");
     return DLSA_E_UNSUPPORTED;
   }
+  if (family == FAMILY_POISSON && P > DLSA_MAX_P_FUSED) {
+    set_error("Poisson fit: P = p + intercept > DLSA_MAX_P_FUSED = " +
+              std::to_string(DLSA_MAX_P_FUSED) + " is not supported");
+    return DLSA_E_UNSUPPORTED;
+  }
   rc = check_fit_args(center, scale, out, f.max_iter, f.tol);
   if (rc != DLSA_OK) return rc;
   if (offsets[K] > 0 && (!X || !y)) {
@@ -124,6 +129,16 @@ int dlsa_logistic_fit_batched_ex(const double* X, const double* y, const int64_t
                    tol, {theta, sig_inv, sig_inv_theta, loglik, iters, status}, opt, stream);
 }
 
+int dlsa_poisson_fit_batched_ex(const double* X, const double* y, const int64_t* offsets,
+                                int32_t K, int32_t p, int32_t fit_intercept,
+                                const double* center, const double* scale, int32_t max_iter,
+                                double tol, double* theta, double* sig_inv,
+                                double* sig_inv_theta, double* loglik, int32_t* iters,
+                                int32_t* status, const dlsa_fit_options* opt, void* stream) {
+  return fit_dense(FAMILY_POISSON, X, y, offsets, K, p, fit_intercept, center, scale, max_iter,
+                   tol, {theta, sig_inv, sig_inv_theta, loglik, iters, status}, opt, stream);
+}
+
 int dlsa_logistic_fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
                                   const int64_t* offsets, int32_t K, int32_t q, int32_t F,
                                   const int32_t* levels, int32_t fit_intercept,
@@ -168,7 +183,7 @@ int dlsa_logistic_fit_batched(const double* X, const double* y, const int64_t* o
                                       iters, status, nullptr, stream);
 }
 
-static int loglik_dense(const double* X, const double* y, const int64_t* offsets, int32_t K,
+static int loglik_dense(int family, const double* X, const double* y, const int64_t* offsets, int32_t K,
                         int32_t p, int32_t fit_intercept, const double* center,
                         const double* scale, const double* betas, int32_t n_beta,
                         double* loglik, double* loglik_sum, void* stream_) {
@@ -179,7 +194,9 @@ static int loglik_dense(const double* X, const double* y, const int64_t* offsets
   const int P = p + (fit_intercept ? 1 : 0);
   if (p < 0 || P < 1 || P > 512 || n_beta < 1 || n_beta > 16 || !betas || !loglik ||
       (center == nullptr) != (scale == nullptr)) {
-    set_error("dlsa_logistic_loglik_batched: invalid arguments (1 <= P <= 512, 1 <= n_beta <= 16)");
+    set_error(std::string(family == FAMILY_POISSON ? "dlsa_poisson_loglik_batched_sum"
+                                                   : "dlsa_logistic_loglik_batched") +
+              ": invalid arguments (1 <= P <= 512, 1 <= n_beta <= 16)");
     return DLSA_E_INVALID;
   }
   const int64_t n_total = offsets[K];
@@ -225,7 +242,7 @@ static int loglik_dense(const double* X, const double* y, const int64_t* offsets
     const int PM = ((P + 7) / 8) * 8;
     const int budget = 160 * 1024 - (n_beta * PM + 2 * PM + 64) * 8;
     ea.nslot = std::max(2, std::min(budget / ea.slot_bytes, 6));
-    DLSA_HIP_TRY(launch_loglik_eval(ea, pl.n_chunks, stream));
+    DLSA_HIP_TRY(launch_loglik_eval(ea, family, pl.n_chunks, stream));
   }
   DLSA_HIP_TRY(launch_loglik_reduce(d_partial, d_pcb, K, n_beta, loglik, stream));
   if (loglik_sum) DLSA_HIP_TRY(launch_loglik_total(loglik, K, n_beta, loglik_sum, stream));
@@ -238,8 +255,8 @@ int dlsa_logistic_loglik_batched(const double* X, const double* y, const int64_t
                                  const double* center, const double* scale,
                                  const double* betas, int32_t n_beta, double* loglik,
                                  void* stream) {
-  return loglik_dense(X, y, offsets, K, p, fit_intercept, center, scale, betas, n_beta, loglik,
-                      nullptr, stream);
+  return loglik_dense(FAMILY_LOGISTIC, X, y, offsets, K, p, fit_intercept, center, scale, betas,
+                      n_beta, loglik, nullptr, stream);
 }
 
 int dlsa_logistic_loglik_batched_sum(const double* X, const double* y, const int64_t* offsets,
@@ -247,8 +264,17 @@ int dlsa_logistic_loglik_batched_sum(const double* X, const double* y, const int
                                      const double* center, const double* scale,
                                      const double* betas, int32_t n_beta, double* loglik,
                                      double* loglik_sum, void* stream) {
-  return loglik_dense(X, y, offsets, K, p, fit_intercept, center, scale, betas, n_beta, loglik,
-                      loglik_sum, stream);
+  return loglik_dense(FAMILY_LOGISTIC, X, y, offsets, K, p, fit_intercept, center, scale, betas,
+                      n_beta, loglik, loglik_sum, stream);
+}
+
+int dlsa_poisson_loglik_batched_sum(const double* X, const double* y, const int64_t* offsets,
+                                    int32_t K, int32_t p, int32_t fit_intercept,
+                                    const double* center, const double* scale,
+                                    const double* betas, int32_t n_beta, double* loglik,
+                                    double* loglik_sum, void* stream) {
+  return loglik_dense(FAMILY_POISSON, X, y, offsets, K, p, fit_intercept, center, scale, betas,
+                      n_beta, loglik, loglik_sum, stream);
 }
 
 int dlsa_logistic_loglik_categorical(const double* Xn, const uint8_t* codes, const double* y,

@@ -31,7 +31,8 @@ enum : int32_t {
 };
 constexpr int kRunPhases = 3;
 enum : int32_t { STATUS_RUNNING = -1 };
-enum : int32_t { FAMILY_LOGISTIC = 0, FAMILY_GAUSSIAN = 1 };
+// FAMILY_POISSON (log link): iterative like the logistic family; fused path only
+enum : int32_t { FAMILY_LOGISTIC = 0, FAMILY_GAUSSIAN = 1, FAMILY_POISSON = 2 };
 
 // Cache policy of the LDS-DMA loads that stream X (the aux / cpol operand of
 // buffer_load ... lds; profiling builds override it, tools/build_variants.sh).
@@ -88,6 +89,11 @@ struct PassArgs {
   // count of the solve before, for a pass enqueued before the host read it
   const int32_t* zrec_gate;
   int32_t waves;  // fp64 per-wave pass geometry (dlsa_fit_options.exact_waves; 0 = auto)
+  // FAMILY_POISSON, fp64 passes: [n_chunks] partial sums of -lgamma(y + 1), the
+  // log-likelihood's constant term.  slab_ll is the constant-free sum
+  // y eta - mu in every pass (what the step halving compares); the constant
+  // is added where loglik is published (newton_solve.hip)
+  double* slab_llc;
 };
 
 // A/B knobs of profiling builds.  The product library reads no environment
@@ -137,6 +143,34 @@ __device__ __forceinline__ double dpp_f64(double v) {
   return __hiloint2double(hi, lo);
 }
 
+// lgamma(y + 1) for y >= 0, the constant term of the Poisson log-likelihood.
+// x = y + 1 is shifted up to z >= 8 by lgamma(x) = lgamma(x + n) - log(x (x + 1)
+// ... (x + n - 1)) (n <= 7, the product <= 8!), then Stirling's series to
+// z^-13 (the next term is < 1e-15 at z = 8).  Two logs, one division, no
+// branches: about a fifth of the library lgamma's instructions and none of
+// its registers (in the per-wave fp64 pass, whose accumulators fill the
+// register file, the library call spilled ~100 VGPRs).  Absolute error
+// ~1e-15 + a few ulps of the value (tests/test_cpu_poisson.py restates it);
+// the terms are summed over rows, so that is what counts.
+__host__ __device__ __forceinline__ double lgamma1p(double y) {
+  double z = y + 1.0, pr = 1.0;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const bool up = z < 8.0;
+    pr = up ? pr * z : pr;
+    z = up ? z + 1.0 : z;
+  }
+  const double r = 1.0 / z, r2 = r * r;
+  double s = 1.0 / 156.0;
+  s = fma(s, r2, -691.0 / 360360.0);
+  s = fma(s, r2, 1.0 / 1188.0);
+  s = fma(s, r2, -1.0 / 1680.0);
+  s = fma(s, r2, 1.0 / 1260.0);
+  s = fma(s, r2, -1.0 / 360.0);
+  s = fma(s, r2, 1.0 / 12.0);
+  return fma(z - 0.5, log(z), -z) + 0.91893853320467274178 + s * r - log(pr);
+}
+
 // Arguments of the per-partition Newton update.
 struct SolveArgs {
   const int32_t* part_chunk_begin;  // [K+1]
@@ -159,13 +193,18 @@ struct SolveArgs {
   double* loglik;       // [K] out
   int32_t P;
   int32_t NT;
-  int32_t family;  // FAMILY_LOGISTIC: Newton to tol; FAMILY_GAUSSIAN: one exact step
+  int32_t family;  // FAMILY_LOGISTIC / FAMILY_POISSON: Newton to tol; FAMILY_GAUSSIAN: one exact step
   int32_t subsample;  // 1 on a warm-start level (row prefix of each partition)
   double tol;
   double switch_tol;
   double level_tol;   // warm-start level: stop when max|step| <= level_tol (1+max|theta|)
   int32_t escalate_to;  // next phase of a stalled PHASE_F32 partition (PHASE_F32X / PHASE_F64)
   int32_t eval_only;    // polish: publish Sig_inv / loglik at the current theta, no step
+  // FAMILY_POISSON (null otherwise): slab_llc of the pass (PassArgs), and
+  // theta0 [K], the start value of parameter 0 (log of the partition's mean y
+  // with an intercept, else 0) a restarted partition goes back to
+  double* slab_llc;
+  const double* theta0;
 };
 
 // Step control of the Newton update (stall escalation, step halving,
@@ -350,7 +389,7 @@ hipError_t launch_wide_assemble(const WideArgs& a, const int32_t* gcb, double* H
 hipError_t launch_wide_newton(const SolveArgs& sa, const WideArgs& wa, const int32_t* rcb,
                               const int32_t* gcb, double* Hfull, int K, hipStream_t s);
 int wide_newton_lds_bytes(int NB);
-hipError_t launch_loglik_eval(const EvalArgs& a, int n_chunks, hipStream_t s);
+hipError_t launch_loglik_eval(const EvalArgs& a, int family, int n_chunks, hipStream_t s);
 hipError_t launch_loglik_reduce(const double* partial, const int32_t* pcb, int K, int B,
                                 double* out, hipStream_t s);
 int eval_slot_bytes(int p);
@@ -382,7 +421,14 @@ hipError_t launch_fit_init(const int64_t* offsets_dev, int K, int P, int start_p
                            double* sig_inv, double* loglik, hipStream_t s);
 hipError_t launch_level_reset(int K, int P, int start_phase, int32_t* phase, int32_t* status,
                               double* ll_prev, int32_t* backtracks, double* theta,
-                              int32_t* counters, hipStream_t s);
+                              int32_t* counters, hipStream_t s, const double* theta0 = nullptr);
+// Poisson start point (aux_kernels.hip): per partition one fixed-order pass
+// over y; theta0[k] = log(mean y) (intercept) or 0, written to theta[k][0]; a
+// negative or non-finite y ends the partition NONFINITE, sum y = 0 SINGULAR
+// (phase PHASE_DONE, outputs left zeroed by fit_init)
+hipError_t launch_poisson_start(const double* y, const int64_t* offsets_dev, int K, int P,
+                                int intercept, double* theta, double* theta0, int32_t* phase,
+                                int32_t* status, hipStream_t s);
 hipError_t launch_polish_mark(int K, int32_t* phase, const int32_t* status, int32_t* counters,
                               hipStream_t s);
 // theta_rec[k] = theta[k] for the partitions in phase `ph` (before a pass

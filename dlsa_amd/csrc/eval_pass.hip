@@ -59,6 +59,9 @@ int eval_slot_bytes(int p) {
   return 16 + d * EW * 1024 + ((p + 8) / 8) * 8 * 8 + ERB * 8;
 }
 
+// FAM: FAMILY_LOGISTIC, or FAMILY_POISSON (y eta - exp(eta) - lgamma(y + 1), the
+// full log-likelihood; the constant once per row, not per candidate)
+template <int FAM>
 __global__ __launch_bounds__(256) void loglik_eval_kernel(const EvalArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int chunk = blockIdx.x;
@@ -140,11 +143,18 @@ __global__ __launch_bounds__(256) void loglik_eval_kernel(const EvalArgs a) {
         if (b < B) eta[b] = fma(v, bet[b * PM + f], eta[b]);
     }
     const double yv = ys[rB];
+    double lg = 0.0;  // lgamma(y + 1): 0 at y = 0 and y = 1
+    if constexpr (FAM == FAMILY_POISSON)
+      if (valid && sl == 0 && yv != 0.0 && yv != 1.0) lg = lgamma1p(yv);
 #pragma unroll
     for (int b = 0; b < EMAXB; ++b) {
       if (b < B) {
         const double e = ev_red8(eta[b]);
-        if (valid && sl == 0) llacc[b] += yv * e - (fmax(e, 0.0) + log1p(exp(-fabs(e))));
+        if constexpr (FAM == FAMILY_POISSON) {
+          if (valid && sl == 0) llacc[b] += yv * e - exp(e) - lg;
+        } else {
+          if (valid && sl == 0) llacc[b] += yv * e - (fmax(e, 0.0) + log1p(exp(-fabs(e))));
+        }
       }
     }
   }
@@ -168,15 +178,17 @@ __global__ __launch_bounds__(256) void loglik_eval_kernel(const EvalArgs a) {
   }
 }
 
-hipError_t launch_loglik_eval(const EvalArgs& a, int n_chunks, hipStream_t s) {
+hipError_t launch_loglik_eval(const EvalArgs& a, int family, int n_chunks, hipStream_t s) {
   const int PM = ((a.P + 7) / 8) * 8;
   const size_t lds = (size_t)a.nslot * a.slot_bytes +
                      ((size_t)a.nbeta * PM + 2 * PM + EW * EMAXB) * sizeof(double);
+  auto kern = family == FAMILY_POISSON ? loglik_eval_kernel<FAMILY_POISSON>
+                                       : loglik_eval_kernel<FAMILY_LOGISTIC>;
   {
-    hipError_t e = ensure_max_lds((const void*)loglik_eval_kernel, 160 * 1024);
+    hipError_t e = ensure_max_lds((const void*)kern, 160 * 1024);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(loglik_eval_kernel, dim3(n_chunks), dim3(256), lds, s, a);
+  hipLaunchKernelGGL(kern, dim3(n_chunks), dim3(256), lds, s, a);
   return hipGetLastError();
 }
 

@@ -368,7 +368,7 @@ inline hipError_t reenter_level(const SolveArgs& sa, int K, int start_phase, con
   hipError_t e = hipMemsetAsync(sa.counters, 0, 16, s);
   if (e == hipSuccess)
     e = launch_level_reset(K, sa.P, start_phase, sa.phase, sa.status, sa.ll_prev, sa.backtracks,
-                           sa.theta, sa.counters, s);
+                           sa.theta, sa.counters, s, sa.theta0);
   if (e == hipSuccess) e = read_counters(sa, K, h, n_running, s);
   return e;
 }

@@ -78,6 +78,7 @@ void FusedFit::set_pass_args(const Plan& pl, const Workspace& ws, const Layout& 
   pa.slab_H = (double*)ws.at(L.off_slabH);
   pa.slab_g = (double*)ws.at(L.off_slabg);
   pa.slab_ll = (double*)ws.at(L.off_slabll);
+  pa.slab_llc = sa.slab_llc;
   if (n_total > 0) {
     const uintptr_t xend = (uintptr_t)(f.X + n_total * (int64_t)f.p);
     pa.x_last16 = ((xend + 15) & ~(uintptr_t)15) - 16;
@@ -215,7 +216,7 @@ int FusedFit::run() {
   const int64_t* offsets = f.offsets;
   // warm-start levels: Newton on row prefixes (1/16) before all rows
   const std::vector<Plan> plans =
-      level_plans(offsets, K, f.p, f.fit_intercept, family == FAMILY_LOGISTIC && opt.warm_start,
+      level_plans(offsets, K, f.p, f.fit_intercept, family != FAMILY_GAUSSIAN && opt.warm_start,
                   [&](double, int64_t) { return opt.rows_per_chunk; });
   const Plan& pl = plans.back();
   const Layout L = make_layout(pl, K);
@@ -248,11 +249,26 @@ int FusedFit::run() {
   sa.switch_tol = opt.switch_tol;
   // a stalled bf16-steered partition goes on with fp32-MFMA Hessians first
   sa.escalate_to = approx_prec == PREC_BF16 ? PHASE_F32X : PHASE_F64;
+  // Poisson: the K start values and the per-chunk constant-term partials live
+  // in an allocation of the fit's own (the workspace layout is the logistic one)
+  Workspace pws(stream);
+  if (family == FAMILY_POISSON) {
+    Bump pb;
+    const int64_t off_t0 = pb.take(8LL * std::max(K, 1));
+    const int64_t off_llc = pb.take(8LL * std::max(pl.n_chunks, 1));
+    if (int rc = pws.alloc(pb.o)) return rc;
+    DLSA_HIP_TRY(hipMemsetAsync(pws.at(0), 0, pb.o, stream));
+    sa.theta0 = (const double*)pws.at(off_t0);
+    sa.slab_llc = (double*)pws.at(off_llc);
+  }
   set_pass_args(pl, ws, L);
 
   const int start_phase =
       (opt.hessian_mode == DLSA_HESSIAN_FP64 || family == FAMILY_GAUSSIAN) ? PHASE_F64 : PHASE_F32;
   DLSA_HIP_TRY(fit_init(sa, d_offsets, K, start_phase, stream));
+  if (family == FAMILY_POISSON)  // the start point; ends the partitions that have no MLE
+    DLSA_HIP_TRY(launch_poisson_start(f.y, d_offsets, K, P, f.fit_intercept ? 1 : 0, sa.theta,
+                                      const_cast<double*>(sa.theta0), sa.phase, sa.status, stream));
   int n_running[kRunPhases] = {0, 0, 0};
   for (int k = 0; k < K; ++k)
     if (offsets[k + 1] > offsets[k]) n_running[start_phase]++;
@@ -261,8 +277,9 @@ int FusedFit::run() {
   h_route = h.phase + K;
   const bool trace = trace_enabled();
 
-  use_oz = opt.exact_pass != DLSA_EXACT_FP64 && approx_prec == PREC_BF16 &&
-           oz_applies(pl.NT, f.p) && pl.max_chunk_rows <= kOzMaxRows;
+  // (Poisson weights are unbounded: no int8 exact pass, DLSA_EXACT_AUTO is fp64 MFMA)
+  use_oz = family != FAMILY_POISSON && opt.exact_pass != DLSA_EXACT_FP64 &&
+           approx_prec == PREC_BF16 && oz_applies(pl.NT, f.p) && pl.max_chunk_rows <= kOzMaxRows;
   d_colmax = (uint32_t*)ws.at(L.off_colmax);
   d_zcolmax = (uint32_t*)ws.at(L.off_zcolmax);
   d_threc = (double*)ws.at(L.off_threc);
@@ -285,6 +302,11 @@ int FusedFit::run() {
       DLSA_HIP_TRY(reenter_level(sa, K, start_phase, h, n_running, stream));
     else
       DLSA_HIP_TRY(read_phases(sa, K, h, stream));
+    if (lvl == 0 && family == FAMILY_POISSON) {  // less the partitions the start point ended
+      n_running[start_phase] = 0;
+      for (int k = 0; k < K; ++k)
+        if (h.phase[k] == start_phase) n_running[start_phase]++;
+    }
     // the prefix MLE is ~sqrt(P/n) from the full one (max step ~0.35 entering
     // the full level at config 2), so a level need not converge: it stops at
     // a 0.2-relative step (warm_level_tol)
@@ -324,7 +346,7 @@ int FusedFit::run() {
   // polish: partitions the budget left running (any phase) get one exact pass
   // at the theta they return; its X^T W X is published as Sig_inv, no step
   // (models.py:114,130 evaluate the weights at the coef sklearn stopped at)
-  if (family == FAMILY_LOGISTIC && running_total(n_running) > 0 && pl.n_chunks > 0) {
+  if (family != FAMILY_GAUSSIAN && running_total(n_running) > 0 && pl.n_chunks > 0) {
     // (the final level's plan, pl, is on the device: it was the last uploaded)
     // a partition stopped in an approximate phase took a full step after its
     // last record: its polish pass cannot use that record

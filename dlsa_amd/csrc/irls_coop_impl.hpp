@@ -298,6 +298,7 @@ void irls_coop_kernel(const PassArgs a) {
 #pragma unroll
   for (int m = 0; m < M; ++m) asm volatile("" : "+v"(beta[m]));
   double llacc = 0.0;
+  [[maybe_unused]] double llcacc = 0.0;  // Poisson fp64 pass: -sum lgamma(y + 1)
   // CM: running max of |x| per feature, kept as the high dword of |x| (what
   // the digit exponents read: ozk::xbound sets the low dword to all ones) --
   // 32-bit integer max instead of a v_max_f64 per value, half the registers.
@@ -416,6 +417,20 @@ void irls_coop_kernel(const PassArgs a) {
           const double sp = (PREC == PREC_F64) ? log1p(ea) : (double)__logf(1.0f + (float)ea);
           llacc += yv * e - (fmax(e, 0.0) + sp);
         }
+      } else if constexpr (FAM == FAMILY_POISSON) {
+        // log link: mu = w = exp(eta).  A padded row's eta is never
+        // exponentiated (its w and r are zeroed below either way).  llacc is
+        // the constant-free sum y eta - mu in every precision -- the quantity
+        // the step halving compares across passes; the constant -lgamma(y + 1)
+        // goes to its own sum, in the fp64 pass only (it is published there)
+        const double mu = exp(valid ? e : 0.0);
+        w = mu;
+        r = yv - mu;
+        if (valid && sl == 0) {
+          llacc += yv * e - mu;
+          if constexpr (PREC == PREC_F64)
+            if (yv != 0.0 && yv != 1.0) llcacc -= lgamma1p(yv);  // 0 at y = 0, 1
+        }
       } else {  // gaussian (OLS): mu = eta, w = 1, ll = -rss/2
         w = 1.0;
         r = yv - e;
@@ -500,6 +515,12 @@ void irls_coop_kernel(const PassArgs a) {
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) llacc += __shfl_xor(llacc, o);
   if (lane == 0) red[W * G::PMAX + wid] = llacc;
+  constexpr bool LLC = FAM == FAMILY_POISSON && PREC == PREC_F64;
+  if constexpr (LLC) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) llcacc += __shfl_xor(llcacc, o);
+    if (lane == 0) red[W * G::PMAX + W + wid] = llcacc;
+  }
   __syncthreads();
   for (int f = tid; f < G::PMAX; f += 64 * W) {
     double s = 0.0;
@@ -512,6 +533,12 @@ void irls_coop_kernel(const PassArgs a) {
 #pragma unroll
     for (int w = 0; w < W; ++w) s += red[W * G::PMAX + w];
     a.slab_ll[chunk] = s;
+    if constexpr (LLC) {
+      double c = 0.0;
+#pragma unroll
+      for (int w = 0; w < W; ++w) c += red[W * G::PMAX + W + w];
+      a.slab_llc[chunk] = c;
+    }
   }
   if constexpr (CM) {
     __syncthreads();  // red is reused
@@ -568,6 +595,7 @@ static hipError_t launch_coop_ntw(const PassArgs& a, int prec, bool std_, int fa
     return std_ ? launch_c<NT, W, PREC_F64, true, FAMILY_GAUSSIAN>(a, n_chunks, s)
                 : launch_c<NT, W, PREC_F64, false, FAMILY_GAUSSIAN>(a, n_chunks, s);
   }
+  if (family == FAMILY_POISSON) return hipErrorInvalidValue;  // launch_coop_poisson_nt
   switch (prec) {
     case PREC_BF16:
       if constexpr (NT <= kOzMaxNT) {
@@ -590,6 +618,27 @@ static hipError_t launch_coop_ntw(const PassArgs& a, int prec, bool std_, int fa
     default:
       return std_ ? launch_c<NT, W, PREC_F64, true, FAMILY_LOGISTIC>(a, n_chunks, s)
                   : launch_c<NT, W, PREC_F64, false, FAMILY_LOGISTIC>(a, n_chunks, s);
+  }
+}
+
+// Poisson family: never records digit scales (CM = 0: no int8 exact pass).
+// Instantiated by the irls_coop_pois_g*.hip units only.
+template <int NT>
+static hipError_t launch_coop_poisson_nt(const PassArgs& a, int prec, bool std_, int n_chunks,
+                                         hipStream_t s) {
+  constexpr int W = coop_waves(NT);
+  if (a.colmax || a.zcolmax) return hipErrorInvalidValue;
+  switch (prec) {
+    case PREC_BF16:
+      return std_ ? launch_c<NT, W, PREC_BF16, true, FAMILY_POISSON>(a, n_chunks, s)
+                  : launch_c<NT, W, PREC_BF16, false, FAMILY_POISSON>(a, n_chunks, s);
+    case PREC_F32:
+      return std_ ? launch_c<NT, W, PREC_F32, true, FAMILY_POISSON>(a, n_chunks, s)
+                  : launch_c<NT, W, PREC_F32, false, FAMILY_POISSON>(a, n_chunks, s);
+    default:
+      if (!a.slab_llc) return hipErrorInvalidValue;
+      return std_ ? launch_c<NT, W, PREC_F64, true, FAMILY_POISSON>(a, n_chunks, s)
+                  : launch_c<NT, W, PREC_F64, false, FAMILY_POISSON>(a, n_chunks, s);
   }
 }
 

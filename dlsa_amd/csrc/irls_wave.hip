@@ -7,14 +7,22 @@ namespace dlsa {
 
 hipError_t launch_irls_wave_g2(const PassArgs& a, int NT, bool std_, int family, int n_chunks,
                                hipStream_t s);
+// the Poisson family's instantiations (irls_wave_pois_g*.hip)
+hipError_t launch_irls_wave_pois_g1(const PassArgs& a, int NT, bool std_, int n_chunks,
+                                    hipStream_t s);
+hipError_t launch_irls_wave_pois_g2(const PassArgs& a, int NT, bool std_, int n_chunks,
+                                    hipStream_t s);
 
-// (the logistic ring is the larger one)
+// (the logistic ring is the larger one; the Poisson pass has its geometry)
 int wave_lds_bytes(int NT, int p) {
   return wave_lds_bytes_impl(NT, wave_rb(NT, wave_w(NT), FAMILY_LOGISTIC), p);
 }
 
 hipError_t launch_irls_wave(const PassArgs& a, int NT, bool standardize, int family, int n_chunks,
                             hipStream_t s) {
+  if (family == FAMILY_POISSON)
+    return NT <= 6 ? launch_irls_wave_pois_g1(a, NT, standardize, n_chunks, s)
+                   : launch_irls_wave_pois_g2(a, NT, standardize, n_chunks, s);
   switch (NT) {
     case 1: return launch_wave_nt<1>(a, standardize, family, n_chunks, s);
     case 2: return launch_wave_nt<2>(a, standardize, family, n_chunks, s);

@@ -317,6 +317,7 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
 #pragma unroll
   for (int m = 0; m < M; ++m) gacc[m] = 0.0;
   double llacc = 0.0;
+  [[maybe_unused]] double llcacc = 0.0;  // Poisson: -sum lgamma(y + 1)
   wd4 acc[TW];           // 16x16x4 tiles (AGPRs)
   double sacc[TW][NSA];  // strip sub-blocks (the unused entries of either are dead)
 #pragma unroll
@@ -395,6 +396,18 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
         w = ea * inv * inv;  // mu (1 - mu), cancellation free
         r = yv - mu;
         if (valid && sl == 0) llacc += yv * e - (fmax(e, 0.0) + wv_log12(1.0 + ea));
+      } else if constexpr (FAM == FAMILY_POISSON) {
+        // log link: mu = w = exp(eta); a padded row's eta is never
+        // exponentiated.  llacc is the constant-free sum y eta - mu (what the
+        // step halving compares, as in the approximate passes); the constant
+        // -lgamma(y + 1) has its own sum, added where loglik is published
+        const double mu = exp(valid ? e : 0.0);
+        w = mu;
+        r = yv - mu;
+        if (valid && sl == 0) {
+          llacc += yv * e - mu;
+          if (yv != 0.0 && yv != 1.0) llcacc -= lgamma1p(yv);  // 0 at y = 0, 1
+        }
       } else {  // gaussian (OLS): mu = eta, w = 1, ll = -rss / 2
         w = 1.0;
         r = yv - e;
@@ -493,7 +506,13 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
   }
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) llacc += __shfl_xor(llacc, o);
-  double* red = (double*)smem;  // the ring is no longer needed: [W - 1][PMAX + 1]
+  constexpr bool LLC = FAM == FAMILY_POISSON;
+  if constexpr (LLC) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) llcacc += __shfl_xor(llcacc, o);
+  }
+  // the ring is no longer needed: [W - 1][PMAX + 1], then (Poisson) [W - 1]
+  double* red = (double*)smem;
   if constexpr (W > 1) {
     __syncthreads();
     if constexpr (WID > 0) {
@@ -501,6 +520,8 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
       for (int m = 0; m < M; ++m)
         if (rl == 0) red[(WID - 1) * (PMAX + 1) + sl + LPR * m] = gacc[m];
       if (lane == 0) red[(WID - 1) * (PMAX + 1) + PMAX] = llacc;
+      if constexpr (LLC)
+        if (lane == 0) red[(W - 1) * (PMAX + 1) + WID - 1] = llcacc;
     }
     __syncthreads();
   }
@@ -516,6 +537,12 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
 #pragma unroll
     for (int w = 1; w < W; ++w) ll += red[(w - 1) * (PMAX + 1) + PMAX];
     if (lane == 0) a.slab_ll[cx.chunk] = ll;
+    if constexpr (LLC) {
+      double c = llcacc;
+#pragma unroll
+      for (int w = 1; w < W; ++w) c += red[(W - 1) * (PMAX + 1) + w - 1];
+      if (lane == 0) a.slab_llc[cx.chunk] = c;
+    }
   }
 }
 
@@ -621,8 +648,18 @@ static hipError_t launch_wave_nt(const PassArgs& a, bool std_, int family, int n
   if (family == FAMILY_GAUSSIAN)
     return std_ ? launch_wave_sf<NT, true, FAMILY_GAUSSIAN>(a, n_chunks, s)
                 : launch_wave_sf<NT, false, FAMILY_GAUSSIAN>(a, n_chunks, s);
+  if (family == FAMILY_POISSON) return hipErrorInvalidValue;  // launch_wave_poisson_nt
   return std_ ? launch_wave_sf<NT, true, FAMILY_LOGISTIC>(a, n_chunks, s)
               : launch_wave_sf<NT, false, FAMILY_LOGISTIC>(a, n_chunks, s);
+}
+
+// Poisson family (instantiated by the irls_wave_pois_g*.hip units only)
+template <int NT>
+static hipError_t launch_wave_poisson_nt(const PassArgs& a, bool std_, int n_chunks,
+                                         hipStream_t s) {
+  if (!a.slab_llc) return hipErrorInvalidValue;
+  return std_ ? launch_wave_sf<NT, true, FAMILY_POISSON>(a, n_chunks, s)
+              : launch_wave_sf<NT, false, FAMILY_POISSON>(a, n_chunks, s);
 }
 
 }  // namespace dlsa

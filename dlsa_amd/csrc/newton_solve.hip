@@ -156,7 +156,10 @@ __global__ __launch_bounds__(NTHR) void newton_solve_kernel(const SolveArgs a) {
       const int i = e / P, j = e - i * P;
       S[e] = H[i >= j ? tri(i, j) : tri(j, i)];
     }
-    if (tid == 0) a.loglik[k] = ll;
+    // Poisson: ll is the constant-free sum the step control compares; the
+    // constant -sum lgamma(y + 1) of the fp64 pass is added here, where the
+    // value is returned (the final publication is always an fp64 pass's)
+    if (tid == 0) a.loglik[k] = (a.slab_llc && phase == PHASE_F64) ? ll + a.slab_llc[cb] : ll;
   }
   if (a.eval_only) return;  // polish: Sig_inv at the returned theta, no step
   __syncthreads();
@@ -408,6 +411,13 @@ __global__ __launch_bounds__(256) void partials_sum_kernel(const SolveArgs a, in
     for (int c = lane; c < n; c += 64) s += ll[c];
     s = wave_sum(s);
     if (lane == 0) ll[0] = s;
+    if (a.slab_llc && a.phase[k] == PHASE_F64) {  // Poisson: the fp64 pass's constant term
+      double* lc = a.slab_llc + cb;
+      double c = 0.0;
+      for (int i = lane; i < n; i += 64) c += lc[i];
+      c = wave_sum(c);
+      if (lane == 0) lc[0] = c;
+    }
   }
 }
 

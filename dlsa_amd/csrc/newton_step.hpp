@@ -71,11 +71,12 @@ __device__ __forceinline__ int32_t approx_backtrack_phase(const SolveArgs& a, in
 
 // A warm-start level that fails (separation, too few rows) only restarts the
 // partition from theta = 0 on the next level (level_reset_kernel rewrites
-// ll_prev and backtracks before that level reads them).
+// ll_prev and backtracks before that level reads them); a Poisson partition
+// restarts from its start point (a.theta0: log mean y on the intercept).
 template <int NTHR>
 __device__ __forceinline__ void level_fail(const SolveArgs& a, int k, int it) {
   double* th = a.theta + (int64_t)k * a.P;
-  for (int f = threadIdx.x; f < a.P; f += NTHR) th[f] = 0.0;
+  for (int f = threadIdx.x; f < a.P; f += NTHR) th[f] = (f == 0 && a.theta0) ? a.theta0[k] : 0.0;
   if (threadIdx.x == 0) {
     a.phase[k] = PHASE_LEVEL_DONE;
     a.iters[k] = it + 1;
@@ -84,7 +85,10 @@ __device__ __forceinline__ void level_fail(const SolveArgs& a, int k, int it) {
 
 // Given the pass's summed log-likelihood ll (llp: the previous point's):
 // false when the iteration ends here (block-uniform).
-//  - ll not finite: the level fails, or the partition ends NONFINITE;
+//  - ll not finite: the level fails, or the partition ends NONFINITE --
+//    except for Poisson after a step (it > 0, a previous point of this level
+//    on record, backtracks < 40): there exp(eta) overflowed, an overshoot
+//    like any other, and the previous step is halved;
 //  - ll fell: halve the previous step (the role of sklearn's line search).
 //    The threshold is above the fp32-log noise of mixed-mode
 //    log-likelihoods; real overshoots of a Newton step lose far more than
@@ -93,15 +97,18 @@ template <int NTHR>
 __device__ __forceinline__ bool step_prelude(const SolveArgs& a, int k, int phase, int it,
                                              double ll, double llp) {
   const int tid = threadIdx.x, P = a.P;
-  if (!isfinite(ll)) {
+  const bool can_halve = !a.eval_only && it > 0 && a.backtracks[k] < 40;
+  const bool overshoot =  // Poisson: a non-finite ll after a step (llp: this level's last point)
+      a.family == FAMILY_POISSON && !isfinite(ll) && can_halve && isfinite(llp);
+  if (!isfinite(ll) && !overshoot) {
     if (a.subsample)
       level_fail<NTHR>(a, k, it);
     else if (tid == 0)
       a.status[k] = DLSA_STATUS_NONFINITE;
     return false;
   }
-  if (!a.eval_only && a.family == FAMILY_LOGISTIC && it > 0 &&
-      ll < llp - 1e-6 * (1.0 + fabs(llp)) && a.backtracks[k] < 40) {
+  if (overshoot || (can_halve && a.family != FAMILY_GAUSSIAN &&
+                    ll < llp - 1e-6 * (1.0 + fabs(llp)))) {
     const int bt = a.backtracks[k] + 1;
     const double sc = ldexp(1.0, -bt);
     double* th = a.theta + (int64_t)k * P;
@@ -133,7 +140,7 @@ __device__ __forceinline__ void factor_failed(const SolveArgs& a, int k, int pha
     return;
   }
   if (threadIdx.x != 0) return;
-  if (phase != PHASE_F64 && a.family == FAMILY_LOGISTIC) {
+  if (phase != PHASE_F64 && a.family != FAMILY_GAUSSIAN) {
     const int32_t ph = escalate_phase(a, phase);
     a.phase[k] = ph;
     a.iters[k] = it + 1;

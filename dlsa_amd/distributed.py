@@ -110,7 +110,7 @@ def loglik_sharded(X, y, offsets, betas, fit_intercept=False, center=None, scale
 
 
 def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
-                     group=None, codes=None, levels=None, **fit_kw):
+                     group=None, codes=None, levels=None, family="logistic", **fit_kw):
     """Fit this rank's partitions on its GPU and return the global DLSA result.
 
     X, y, offsets describe the LOCAL shard (rows already on this rank's
@@ -118,10 +118,19 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
     categorical-code layout (``logistic_model_batched_categorical``).  The
     row count N of the DBIC is summed in the same single collective as the
     partition sums (reference: the shuffle + collect of dlsa/dlsa.py:30-34).
+    ``family`` = "logistic" or "poisson" (``poisson_model_batched``: dense
+    layout only); everything after the local fits is the same for both.
     """
-    from .models import logistic_model_batched, logistic_model_batched_categorical
+    from .models import (logistic_model_batched, logistic_model_batched_categorical,
+                         poisson_model_batched)
 
-    if codes is not None:
+    if family not in ("logistic", "poisson"):
+        raise ValueError(f"family must be 'logistic' or 'poisson', not {family!r}")
+    if family == "poisson":
+        if codes is not None:
+            raise ValueError("family='poisson' runs on the dense layout only (no codes)")
+        fit = poisson_model_batched(X, y, offsets, fit_intercept=fit_intercept, **fit_kw)
+    elif codes is not None:
         fit = logistic_model_batched_categorical(X, codes, y, offsets, levels,
                                                  fit_intercept=fit_intercept, **fit_kw)
     else:

@@ -279,30 +279,12 @@ class BatchedFit:
         return {_hip.STATUS_NAMES.get(int(v), str(v)): int((s == v).sum()) for v in np.unique(s)}
 
 
-def logistic_model_batched(X, y, offsets, fit_intercept=False, center=None, scale=None,
-                           max_iter=100, tol=1e-10, hessian="mixed", switch_tol=1e-6,
-                           record_timing=False, rows_per_chunk=0, workspace=None,
-                           device=None, exact="auto", exact_waves=0, oz_max_bytes=0):
-    """Fit K row partitions at once on the GPU (batched Newton/IRLS).
-
-    Per partition k (rows ``offsets[k]:offsets[k+1]`` of X) this computes what
-    ``logistic_model`` returns for one Spark group (models.py:94-131): the
-    unpenalised MLE ``theta_k`` (intercept first when ``fit_intercept``),
-    ``Sig_inv_k = X_k^T diag(p(1-p)) X_k`` at theta_k and
-    ``Sig_inv_k theta_k``.  ``center``/``scale`` standardise the columns like
-    models.py:99-101.
-
-    X: [n, p] fp64 (torch tensor on the GPU, or array-like, copied once);
-    y: [n] 0/1; offsets: K+1 host ints.  ``hessian`` = "mixed" (bf16-MFMA
-    Hessian until the Newton step is below ``switch_tol``, then fp64-MFMA
-    passes; the gradient and the returned Sig_inv are always fp64),
-    "mixed_f32" (fp32-MFMA approximate Hessian) or "fp64".  ``exact`` =
-    "auto" (the exact pass that publishes Sig_inv on the int8 matrix cores,
-    as int8 digit slices, wherever it applies; ~1e-12 per entry) or "fp64"
-    (fp64 MFMA); ``exact_waves`` (0, 1, 2) the fp64 exact pass's geometry
-    for P <= 128 and ``oz_max_bytes`` a cap on the wide path's int8 digit
-    records (include/dlsa_hip.h, dlsa_fit_options).
-    """
+def _glm_model_batched(entry, X, y, offsets, fit_intercept, center, scale, max_iter, tol,
+                       hessian, switch_tol, record_timing, rows_per_chunk, workspace, device,
+                       exact, exact_waves, oz_max_bytes):
+    """The body the iterative families share: checked device copies, outputs,
+    options and workspace, then the C-ABI call ``entry`` (an ``*_fit_batched_ex``
+    symbol).  Returns a BatchedFit."""
     dev = _require_gpu(device)
     Xd = _dev_f64(X, dev)
     yd = _dev_f64(y, dev).reshape(-1)
@@ -350,14 +332,66 @@ def logistic_model_batched(X, y, offsets, fit_intercept=False, center=None, scal
         workspace = torch.empty((max(int(need), 1),), dtype=torch.uint8, device=dev)
     opt.workspace = workspace.data_ptr()
     opt.workspace_bytes = workspace.numel()
-    rc = lib.dlsa_logistic_fit_batched_ex(
+    rc = getattr(lib, entry)(
         _ptr(Xd), _ptr(yd), offs_p, K, p, int(bool(fit_intercept)), _ptr(cd), _ptr(sd),
         int(max_iter), float(tol), _ptr(theta), _ptr(sig), _ptr(sigt), _ptr(ll), _ptr(iters),
         _ptr(status), ctypes.byref(opt), _stream(dev))
-    _hip.check(rc, "dlsa_logistic_fit_batched_ex")
+    _hip.check(rc, entry)
     stats = _hip.last_fit_stats()
     stats["workspace_bytes"] = int(need)
     return BatchedFit(theta, sig, sigt, ll, iters, status, offs, bool(fit_intercept), stats)
+
+
+def logistic_model_batched(X, y, offsets, fit_intercept=False, center=None, scale=None,
+                           max_iter=100, tol=1e-10, hessian="mixed", switch_tol=1e-6,
+                           record_timing=False, rows_per_chunk=0, workspace=None,
+                           device=None, exact="auto", exact_waves=0, oz_max_bytes=0):
+    """Fit K row partitions at once on the GPU (batched Newton/IRLS).
+
+    Per partition k (rows ``offsets[k]:offsets[k+1]`` of X) this computes what
+    ``logistic_model`` returns for one Spark group (models.py:94-131): the
+    unpenalised MLE ``theta_k`` (intercept first when ``fit_intercept``),
+    ``Sig_inv_k = X_k^T diag(p(1-p)) X_k`` at theta_k and
+    ``Sig_inv_k theta_k``.  ``center``/``scale`` standardise the columns like
+    models.py:99-101.
+
+    X: [n, p] fp64 (torch tensor on the GPU, or array-like, copied once);
+    y: [n] 0/1; offsets: K+1 host ints.  ``hessian`` = "mixed" (bf16-MFMA
+    Hessian until the Newton step is below ``switch_tol``, then fp64-MFMA
+    passes; the gradient and the returned Sig_inv are always fp64),
+    "mixed_f32" (fp32-MFMA approximate Hessian) or "fp64".  ``exact`` =
+    "auto" (the exact pass that publishes Sig_inv on the int8 matrix cores,
+    as int8 digit slices, wherever it applies; ~1e-12 per entry) or "fp64"
+    (fp64 MFMA); ``exact_waves`` (0, 1, 2) the fp64 exact pass's geometry
+    for P <= 128 and ``oz_max_bytes`` a cap on the wide path's int8 digit
+    records (include/dlsa_hip.h, dlsa_fit_options).
+    """
+    return _glm_model_batched("dlsa_logistic_fit_batched_ex", X, y, offsets, fit_intercept, center,
+                              scale, max_iter, tol, hessian, switch_tol, record_timing,
+                              rows_per_chunk, workspace, device, exact, exact_waves, oz_max_bytes)
+
+
+def poisson_model_batched(X, y, offsets, fit_intercept=False, center=None, scale=None,
+                          max_iter=100, tol=1e-10, hessian="mixed", switch_tol=1e-6,
+                          record_timing=False, rows_per_chunk=0, workspace=None, device=None,
+                          exact_waves=0):
+    """Fit K row partitions of count data at once on the GPU: Poisson
+    regression with the log link (``dlsa_poisson_fit_batched_ex``).
+
+    Per partition k: eta = x . theta, mu = exp(eta); ``theta_k`` the
+    unpenalised MLE (intercept first when ``fit_intercept``), ``Sig_inv_k =
+    X_k^T diag(mu) X_k`` at theta_k, ``Sig_inv_k theta_k`` and the full
+    log-likelihood ``sum y eta - mu - lgamma(y + 1)``.  y is real, finite and
+    >= 0.  Arguments as ``logistic_model_batched``; the exact passes always run
+    on the fp64 MFMA (the weights are unbounded: no int8 pass).  The fit starts
+    at the intercept-only MLE (log mean y); a partition with a negative or
+    non-finite y gets status "nonfinite", one with sum y = 0 "singular", both
+    with all-zero outputs.  P = p + intercept <= 192 (``DlsaHipError`` above).
+    The BatchedFit feeds ``dlsa_mapred`` / ``reduce_partitions_device`` like a
+    logistic one: the combine step never looks at the likelihood."""
+    return _glm_model_batched("dlsa_poisson_fit_batched_ex", X, y, offsets, fit_intercept, center,
+                              scale, max_iter, tol, hessian, switch_tol, record_timing,
+                              rows_per_chunk, workspace, device, "auto", exact_waves, 0)
 
 
 def _cat_inputs(Xn, codes, y, offsets, levels, center, scale, dev):
@@ -505,14 +539,9 @@ def _loglik_groups(call, betas, P, K, dev, return_sum):
     return (out, total) if return_sum else out
 
 
-def logistic_loglik_batched(X, y, offsets, betas, fit_intercept=False, center=None, scale=None,
-                            device=None, return_sum=False):
-    """Per-partition log-likelihood of candidate coefficient vectors in one
-    pass over X (the evaluation step of dlsa/models.py:151-225 /
-    dlsa/model_eval.py:10-42).  betas: [B, P], intercept first; more than 16
-    candidates are evaluated 16 to a pass.  Returns a [K, B] fp64 tensor on
-    the device; with ``return_sum`` also its [B] sum over the partitions (the
-    group-by sum of model_eval.py:38, fixed order, on the device)."""
+def _loglik_dense(entry, X, y, offsets, betas, fit_intercept, center, scale, device, return_sum):
+    """The dense evaluation pass of one family (``entry``: a
+    ``*_loglik_batched_sum`` symbol) through ``_loglik_groups``."""
     dev = _require_gpu(device)
     Xd = _dev_f64(X, dev)
     yd = _dev_f64(y, dev).reshape(-1)
@@ -525,16 +554,37 @@ def logistic_loglik_batched(X, y, offsets, betas, fit_intercept=False, center=No
     if center is not None or scale is not None:
         cd = _dev_f64(center, dev).reshape(-1)
         sd = _dev_f64(scale, dev).reshape(-1)
-    lib = _hip.load()
+    fn = getattr(_hip.load(), entry)
 
     def call(bd, g, out, total):
-        rc = lib.dlsa_logistic_loglik_batched_sum(
-            _ptr(Xd), _ptr(yd), offs.ctypes.data_as(ctypes.c_void_p), K, p,
-            int(bool(fit_intercept)), _ptr(cd), _ptr(sd), _ptr(bd), g, _ptr(out), _ptr(total),
-            _stream(dev))
-        _hip.check(rc, "dlsa_logistic_loglik_batched_sum")
+        rc = fn(_ptr(Xd), _ptr(yd), offs.ctypes.data_as(ctypes.c_void_p), K, p,
+                int(bool(fit_intercept)), _ptr(cd), _ptr(sd), _ptr(bd), g, _ptr(out), _ptr(total),
+                _stream(dev))
+        _hip.check(rc, entry)
 
     return _loglik_groups(call, betas, p + (1 if fit_intercept else 0), K, dev, return_sum)
+
+
+def logistic_loglik_batched(X, y, offsets, betas, fit_intercept=False, center=None, scale=None,
+                            device=None, return_sum=False):
+    """Per-partition log-likelihood of candidate coefficient vectors in one
+    pass over X (the evaluation step of dlsa/models.py:151-225 /
+    dlsa/model_eval.py:10-42).  betas: [B, P], intercept first; more than 16
+    candidates are evaluated 16 to a pass.  Returns a [K, B] fp64 tensor on
+    the device; with ``return_sum`` also its [B] sum over the partitions (the
+    group-by sum of model_eval.py:38, fixed order, on the device)."""
+    return _loglik_dense("dlsa_logistic_loglik_batched_sum", X, y, offsets, betas, fit_intercept,
+                         center, scale, device, return_sum)
+
+
+def poisson_loglik_batched(X, y, offsets, betas, fit_intercept=False, center=None, scale=None,
+                           device=None, return_sum=False):
+    """``logistic_loglik_batched`` for the Poisson family: per partition and
+    candidate ``sum y eta - exp(eta) - lgamma(y + 1)`` with eta = x . beta
+    (the log-likelihood ``poisson_model_batched`` returns).  Same arguments,
+    limits (P <= 512, 16 candidates to a pass) and outputs."""
+    return _loglik_dense("dlsa_poisson_loglik_batched_sum", X, y, offsets, betas, fit_intercept,
+                         center, scale, device, return_sum)
 
 
 def logistic_loglik_batched_categorical(Xn, codes, y, offsets, levels, betas, fit_intercept=False,

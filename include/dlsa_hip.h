@@ -172,6 +172,9 @@ void dlsa_fit_options_default(dlsa_fit_options* opt);
 
 /* Device scratch needed by a fit with these partitions (offsets: HOST array of
  * K+1 int64).  Pass at least this many bytes in dlsa_fit_options.workspace.
+ * The plan does not depend on the family: the same size serves
+ * dlsa_poisson_fit_batched_ex (whose K start values and constant-term partials
+ * live in a small allocation of the fit's own, on the stream).
  * For P > DLSA_MAX_P_FUSED this includes the int8 digit records of the
  * mixed-mode exact Gram (n * PP * 5 bytes, PP = P rounded up to 128; DESIGN.md
  * 4.4b): a smaller workspace that still holds everything else runs the fp64
@@ -218,6 +221,53 @@ int dlsa_logistic_fit_batched_ex(const double* X, const double* y,
                                  double* sig_inv_theta, double* loglik,
                                  int32_t* iters, int32_t* status,
                                  const dlsa_fit_options* opt, void* stream);
+
+/*
+ * Batched local Poisson regression (log link) -- a third family of the
+ * batched fit; the reference has no counterpart.  Arguments and outputs
+ * exactly as dlsa_logistic_fit_batched_ex.  Per partition:
+ *   eta = x . theta, mu = exp(eta) (intercept first, center/scale as there),
+ *   theta         the unpenalised Poisson MLE,
+ *   sig_inv       X^T diag(mu) X at the returned theta,
+ *   sig_inv_theta sig_inv theta,
+ *   loglik        sum_i y_i eta_i - mu_i - lgamma(y_i + 1), the full
+ *                 log-likelihood (the step control compares the constant-free
+ *                 sum; the constant is added where loglik is returned).
+ * y is real, finite and >= 0 (non-integer y allowed: quasi-likelihood use).
+ * Start point: with an intercept theta = (log mean y_k, 0, ..., 0), the MLE of
+ * the intercept-only model; without one theta = 0.  A partition restarted by
+ * a failed warm-start level goes back to this point.  Two statuses are
+ * decided before any pass, with all-zero outputs: a negative or non-finite y
+ * gives DLSA_STATUS_NONFINITE, sum y = 0 (the MLE does not exist)
+ * DLSA_STATUS_SINGULAR.  A step after which the log-likelihood is not finite
+ * (exp overflow) is halved like one after which it fell.
+ * opt may be NULL.  hessian_mode, exact_waves, warm_start, switch_tol and the
+ * workspace keep their meaning; exact_pass: DLSA_EXACT_AUTO resolves to the
+ * fp64 MFMA (the weights exp(eta) are unbounded: the int8 exact pass does not
+ * apply).  Limit: P <= DLSA_MAX_P_FUSED (192), else DLSA_E_UNSUPPORTED before
+ * any launch.  Workspace: dlsa_logistic_workspace_bytes.
+ */
+int dlsa_poisson_fit_batched_ex(const double* X, const double* y,
+                                const int64_t* offsets, int32_t K, int32_t p,
+                                int32_t fit_intercept, const double* center,
+                                const double* scale, int32_t max_iter,
+                                double tol, double* theta, double* sig_inv,
+                                double* sig_inv_theta, double* loglik,
+                                int32_t* iters, int32_t* status,
+                                const dlsa_fit_options* opt, void* stream);
+
+/*
+ * dlsa_logistic_loglik_batched_sum for the Poisson family:
+ *   loglik[k * n_beta + b] = sum_i y_i eta_i - exp(eta_i) - lgamma(y_i + 1),
+ * eta_i = x_i . beta_b.  Same arguments, limits (P <= 512, 1 <= n_beta <= 16)
+ * and fixed summation order.
+ */
+int dlsa_poisson_loglik_batched_sum(const double* X, const double* y,
+                                    const int64_t* offsets, int32_t K, int32_t p,
+                                    int32_t fit_intercept, const double* center,
+                                    const double* scale, const double* betas,
+                                    int32_t n_beta, double* loglik, double* loglik_sum,
+                                    void* stream);
 
 /*
  * Batched local OLS fit (the linear DLSA path; the
