@@ -1,0 +1,566 @@
+"""Emulator of the batched Newton fit, iterate by iterate (not a test module).
+
+Plain fp64 numpy (torch on the CPU only for the bf16 rounding) restating, for
+ONE partition, the state machine of dlsa_amd/csrc/newton_step.hpp around the
+solve kernels, with the Hessian of each pass built the way the pass that
+would run builds it:
+
+* ``"fp64"``: X^T W X in fp64 (every exact pass, and hessian="fp64").
+* ``"bf16"``: Z^T Z summed in fp64, Z the operand image of the cooperative
+  pass (irls_coop_impl.hpp, stage B) and of the wide fused pass
+  (wide_fused.hip): z = bf16_rne(fl32(fl32(x) * sqrtf(fl32(w)))), x the
+  standardised fp64 value ((x - c) * (1 / s) fused, x * (1 / s) - c * (1 / s)
+  wide), the intercept column x = 1, so z = sqrtf(fl32(w)) there.
+* ``"f32"``: tile_phase<..., PREC_F32, ...> multiplies fl32(w x_i) by
+  fl32(x_j) (w x_i formed in fp64) and accumulates in fp32.  The operand
+  roundings are emulated (lower triangle sum fl32(w x_i) fl32(x_j), mirrored,
+  as the solve kernel assembles it), summed in fp64: the fp32 accumulation is
+  the only part left to the tolerance, and it is the same size as in the bf16
+  pass (chunked_f32_gram).  The operand roundings move a step by ~1e-8 of
+  its size, so the exact H would have been adequate as well; emulating them
+  costs nothing.
+
+The gradient and the log-likelihood are exact fp64 in every mode, as on the
+GPU (the approximate passes' fp32 log only feeds the halving test, whose
+margin tests/test_cpu_newton_ref.py checks).
+
+``trajectory`` returns the iterates, the steps and every decision with its
+margin; ``one_row_defect`` the same trajectory with the partition's last row
+left out of H at one iteration: the yardstick D_m of the GPU tolerance.
+The second half of the file holds the cases tests/test_gpu_newton_steps.py
+runs, so that tests/test_cpu_newton_ref.py checks the same inputs.
+"""
+
+import functools
+
+import numpy as np
+
+import _poisson_ref as R
+import oracle as O
+
+PHASE_F32, PHASE_F32X, PHASE_F64 = 0, 1, 2
+K_STALL_DLL = 1e-5  # newton_step.hpp kStallDll
+HALVE_REL = 1e-6    # step_prelude: ll < llp - 1e-6 (1 + |llp|)
+
+
+# --------------------------------------------------------------------------
+# the pass: weights, gradient, log-likelihood, Hessian by mode
+# --------------------------------------------------------------------------
+
+def _bf16(a32):
+    import torch
+
+    t = torch.from_numpy(np.ascontiguousarray(a32, dtype=np.float32))
+    return t.to(torch.bfloat16).to(torch.float64).numpy()
+
+
+def _bf16_trunc(a32):
+    """bf16 by truncation (a defective conversion; tests of the tests only)."""
+    u = np.ascontiguousarray(a32, dtype=np.float32).view(np.uint32) & np.uint32(0xFFFF0000)
+    return u.view(np.float32).astype(np.float64)
+
+
+class Design:
+    """The fp64 design of one partition and the standardised values the
+    approximate passes round (``path``: "fused" or "wide")."""
+
+    def __init__(self, X, fit_intercept=False, center=None, scale=None, path="fused"):
+        X = np.asarray(X, dtype=np.float64)
+        self.Z = R.design(X, fit_intercept, center, scale)  # the reference's design
+        if center is None:
+            xs = X
+        else:
+            c, inv = np.asarray(center, np.float64), 1.0 / np.asarray(scale, np.float64)
+            xs = (X - c) * inv if path == "fused" else X * inv - c * inv
+        if fit_intercept:
+            xs = np.column_stack([np.ones(X.shape[0]), xs])
+        self.xs = xs
+        self.x32 = xs.astype(np.float32)
+        self.n, self.P = self.Z.shape
+
+
+def weights(family, eta):
+    """(mu, w) as the row phases compute them."""
+    if family == "poisson":
+        with np.errstate(over="ignore"):
+            mu = np.exp(eta)
+        return mu, mu
+    ea = np.exp(-np.abs(eta))
+    inv = 1.0 / (1.0 + ea)
+    return np.where(eta >= 0.0, inv, ea * inv), ea * inv * inv
+
+
+def loglik(family, eta, y):
+    """The sum the step control compares (Poisson: constant-free)."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        if family == "poisson":
+            return float(np.sum(y * eta - np.exp(eta)))
+        return float(np.sum(y * eta - (np.maximum(eta, 0.0) + np.log1p(np.exp(-np.abs(eta))))))
+
+
+def bf16_image(D, w, convert=_bf16):
+    """Z [n, P] as fp64 values of bf16 numbers."""
+    sw = np.sqrt(w.astype(np.float32))  # IEEE fp32 sqrt of fl32(w)
+    return convert(D.x32 * sw[:, None])  # fp32 product, then one rounding to bf16
+
+
+def hessian(D, w, mode, drop_last=False, convert=_bf16):
+    """H of one pass.  ``drop_last``: without the partition's last row."""
+    sl = slice(0, D.n - 1) if drop_last else slice(None)
+    if mode == "fp64":
+        return D.Z[sl].T @ (D.Z[sl] * w[sl, None])
+    if mode == "bf16":
+        Z = bf16_image(D, w, convert)[sl]
+        return Z.T @ Z
+    if mode == "f32":
+        A = (D.xs[sl] * w[sl, None]).astype(np.float32).astype(np.float64)
+        L = np.tril(A.T @ D.x32[sl].astype(np.float64))  # tile (I, J), I >= J: av[I] x xv[J]
+        return L + np.tril(L, -1).T
+    raise ValueError(mode)
+
+
+def chunk_bounds(n, rows_per_chunk):
+    """Row ranges of one partition's chunks (fit_plan.hpp make_plan)."""
+    nc = (n + rows_per_chunk - 1) // rows_per_chunk
+    return [(n * c // nc, n * (c + 1) // nc) for c in range(nc)]
+
+
+def chunked_f32_gram(A, B, rows_per_chunk, block):
+    """A^T B with the accumulation of the approximate passes modelled: one fp32
+    accumulator per chunk that takes the products of ``block`` rows at a time
+    (their sum exact, each addition rounded to fp32; 32 rows per bf16 MFMA, 4
+    per fp32 MFMA), chunks summed in fp64."""
+    n, P = A.shape
+    H = np.zeros((P, P))
+    for a, b in chunk_bounds(n, rows_per_chunk):
+        acc = np.zeros((P, P), dtype=np.float32)
+        for r in range(a, b, block):
+            e = min(r + block, b)
+            acc = (acc.astype(np.float64) + A[r:e].T @ B[r:e]).astype(np.float32)
+        H += acc.astype(np.float64)
+    return H
+
+
+def noisy_hessian(D, w, hm, rows_per_chunk):
+    """H of an approximate pass with chunked_f32_gram in place of the fp64 sum."""
+    if hm == "bf16":
+        Z = bf16_image(D, w)
+        return chunked_f32_gram(Z, Z, rows_per_chunk, 32)
+    A = (D.xs * w[:, None]).astype(np.float32).astype(np.float64)
+    L = np.tril(chunked_f32_gram(A, D.x32.astype(np.float64), rows_per_chunk, 4))
+    return L + np.tril(L, -1).T
+
+
+# --------------------------------------------------------------------------
+# the state machine
+# --------------------------------------------------------------------------
+
+def _margin(value, threshold):
+    """How clearly `value <= threshold` is decided either way: the factor
+    between the two (inf when the value has the other sign or is zero)."""
+    if not np.isfinite(value) or not np.isfinite(threshold):
+        return np.inf
+    if value <= 0.0:
+        return np.inf
+    return max(value / threshold, threshold / value) if threshold > 0 else np.inf
+
+
+def _approx_mode(mode, phase):
+    if phase == PHASE_F64 or mode == "fp64":
+        return "fp64"
+    if phase == PHASE_F32X or mode == "mixed_f32":
+        return "f32"
+    return "bf16"
+
+
+def _run(D, y, family, fit_intercept, mode, max_iter, tol, switch_tol, path, defect_at,
+         convert=_bf16, noisy_rpc=0):
+    y = np.asarray(y, dtype=np.float64)
+    P = D.P
+    theta = np.zeros(P)
+    if family == "poisson" and fit_intercept:
+        theta[0] = np.log(y.sum() / y.size)  # poisson_start_kernel
+    start = theta.copy()
+    phase = PHASE_F64 if mode == "fp64" else PHASE_F32
+    escalate_to = PHASE_F32X if (mode == "mixed" and path == "fused") else PHASE_F64
+    theta_prev, d_prev = theta.copy(), np.zeros(P)
+    ll_prev, bt, stall, dm_prev = -np.inf, 0, 0, 0.0
+    thetas, steps, rec = [], [], []
+    status, it = "maxiter", 0
+
+    def escalate(ph):
+        return escalate_to if ph == PHASE_F32 else PHASE_F64
+
+    def stall_step(ph, stalled):
+        nonlocal stall, dm_prev
+        st = stall + 1 if stalled else 0
+        if st >= 2:
+            stall, dm_prev = 0, 0.0
+            return escalate(ph)
+        stall = st
+        return ph
+
+    while it < max_iter:
+        eta = D.Z @ theta
+        ll = loglik(family, eta, y)
+        r = {"it": it + 1, "phase": phase, "hmode": _approx_mode(mode, phase), "ll": ll,
+             "ll_prev": ll_prev, "halved": False, "switched": False, "escalated": False,
+             "converged": False, "margins": {}}
+        can_halve = it > 0 and bt < 40
+        overshoot = family == "poisson" and not np.isfinite(ll) and can_halve and np.isfinite(ll_prev)
+        if not np.isfinite(ll) and not overshoot:
+            status = "nonfinite"
+            break
+        if can_halve and np.isfinite(ll):
+            r["margins"]["halve"] = _margin(ll_prev - ll, HALVE_REL * (1.0 + abs(ll_prev)))
+        if overshoot or (can_halve and ll < ll_prev - HALVE_REL * (1.0 + abs(ll_prev))):
+            bt += 1
+            theta = theta_prev + np.ldexp(1.0, -bt) * d_prev
+            it += 1
+            if phase != PHASE_F64 and dm_prev > 0.0:  # approx_backtrack_phase
+                nph = stall_step(phase, True)
+                r["escalated"], phase = nph != phase, nph
+            r.update(halved=True, bt=bt, dm=float(np.abs(theta - thetas[-1]).max()))
+            thetas.append(theta.copy())
+            steps.append(np.ldexp(1.0, -bt) * d_prev)
+            rec.append(r)
+            continue
+        mu, w = weights(family, eta)
+        g = D.Z.T @ (y - mu)
+        hm = r["hmode"]
+        if noisy_rpc and hm != "fp64":
+            H = noisy_hessian(D, w, hm, noisy_rpc)
+        else:
+            H = hessian(D, w, hm, drop_last=(defect_at == it + 1), convert=convert)
+        try:
+            np.linalg.cholesky(H)
+            d = np.linalg.solve(H, g)
+        except np.linalg.LinAlgError:
+            d = None
+        if d is None:  # factor_failed
+            it += 1
+            if phase == PHASE_F64:
+                status = "singular"
+                break
+            phase, stall, dm_prev = escalate(phase), 0, 0.0
+            r["escalated"] = True
+            thetas.append(theta.copy())
+            steps.append(np.zeros(P))
+            rec.append(r)
+            continue
+        theta_prev, d_prev = theta.copy(), d.copy()
+        theta = theta + d
+        dm, tm = float(np.abs(d).max()), float(np.abs(theta).max())
+        it += 1
+        r.update(dm=dm, tm=tm)
+        thetas.append(theta.copy())
+        steps.append(d.copy())
+        rec.append(r)
+        if not np.isfinite(dm):
+            theta, status = theta_prev.copy(), "nonfinite"
+            thetas[-1] = theta.copy()
+            break
+        llp, ll_prev, bt = ll_prev, ll, 0
+        if phase != PHASE_F64:
+            r["margins"]["switch"] = _margin(dm, switch_tol * (1.0 + tm))
+            if dm <= switch_tol * (1.0 + tm):
+                phase, r["switched"] = PHASE_F64, True
+            else:  # approx_next_phase
+                quiet_thr = K_STALL_DLL * (1.0 + abs(ll))
+                # the stall rule can only look at dm / dm_prev where the gate
+                # (ll - llp <= quiet_thr) is open or within a factor 10 of it
+                if ll - llp <= 10.0 * quiet_thr and len(rec) > 1 and "dm" in rec[-2]:
+                    r["margins"]["stall"] = _margin(dm, 0.5 * rec[-2]["dm"])
+                    r["stall_ratio"] = dm / rec[-2]["dm"]
+                if not (ll - llp <= quiet_thr):
+                    stall, dm_prev = 0, 0.0
+                else:
+                    nph = stall_step(phase, dm_prev > 0.0 and dm > 0.5 * dm_prev)
+                    if nph == phase:
+                        dm_prev = dm
+                    r["escalated"], phase = nph != phase, nph
+        else:
+            r["margins"]["tol"] = _margin(dm, tol * (1.0 + tm))
+            if dm <= tol * (1.0 + tm):
+                r["converged"], status = True, "ok"
+                break
+    return {"theta": thetas, "step": steps, "rec": rec, "status": status, "iters": it,
+            "start": start, "final": theta}
+
+
+def trajectory(X, y, family="logistic", fit_intercept=False, center=None, scale=None,
+               mode="fp64", max_iter=3, tol=1e-10, switch_tol=1e-6, path="fused",
+               _defect_at=0, _convert=_bf16):
+    """The iterates of one partition.
+
+    ``mode``: the fit's hessian option ("mixed": bf16 image; "mixed_f32";
+    "fp64"); the Hessian of each pass follows the partition's phase, as on the
+    GPU (a switched or escalated partition takes f32 / fp64 Hessians).
+    Returns a dict: ``theta`` [theta_1 .. theta_m], ``step`` (theta_i -
+    theta_{i-1}: the Newton step, or the halved previous step), ``rec`` one
+    record per iteration (phase, Hessian mode, log-likelihoods, halved /
+    switched / escalated / converged, max |d|, and ``margins``: for each
+    decision taken, the factor by which it cleared its threshold), ``status``
+    ("ok", "maxiter", ...), ``iters``, ``start`` and ``final``.
+    """
+    D = X if isinstance(X, Design) else Design(X, fit_intercept, center, scale, path)
+    return _run(D, y, family, fit_intercept, mode, max_iter, tol, switch_tol, path, _defect_at,
+                _convert)
+
+
+def one_row_defect(X, y, m, **kw):
+    """``trajectory`` with max_iter = m, H of iteration m built without the
+    partition's last row (gradient exact, clean theta_{m-1})."""
+    kw["max_iter"] = m
+    return trajectory(X, y, _defect_at=m, **kw)
+
+
+def newton_step(D, y, family, theta, hmode):
+    """theta + H_hmode(theta)^-1 g(theta): one step of the emulator from a
+    given point (the GPU's own previous iterate)."""
+    mu, w = weights(family, D.Z @ theta)
+    return theta + np.linalg.solve(hessian(D, w, hmode), D.Z.T @ (np.asarray(y, np.float64) - mu))
+
+
+def exact_iterations(tr):
+    """1-based iterations the partition spent in the exact phase."""
+    return [r["it"] for r in tr["rec"] if r["phase"] == PHASE_F64]
+
+
+# --------------------------------------------------------------------------
+# distances of one partition: what the GPU tolerance is made of
+# --------------------------------------------------------------------------
+
+def step_yardsticks(D, y, family, fit_intercept, mode, max_iter, rows_per_chunk, path="fused"):
+    """Per checked iteration m = 1 .. max_iter of one partition, a dict:
+
+    theta   the emulated iterate theta_m;
+    s       max |theta_m - theta_{m-1}|;
+    D       the one-row-defect distance max |theta_defect,m - theta_m|.  On a
+            halving iteration (theta_m = theta_j-1 + 2^-bt d_j, no Hessian) it is
+            2^-bt D_j: the defect in the step that is being halved;
+    budget  (approximate modes) max |theta_m(emulated) - theta_m(exact H from
+            the same theta_{m-1})|;
+    noise   (approximate modes) the step moved by the modelled fp32
+            accumulation (chunked_f32_gram) instead of the fp64 sum of the same
+            operands;
+    carried (approximate modes) max |theta_m - theta_m of a trajectory that
+            takes the fp32-accumulated Hessian at every iteration|: the noise of
+            iteration m - 1 moves theta_{m-1} by ~1e-7 s, which moves the
+            weights by about an fp32 ulp and so flips a few bf16 roundings of
+            the next image (each 2^-8 of one entry of Z).  That is what a
+            comparison of whole trajectories sees from m = 2 on.
+    """
+    tr = _run(D, y, family, fit_intercept, mode, max_iter, 1e-10, 1e-6, path, 0)
+    carried = None
+    if mode != "fp64":
+        carried = _run(D, y, family, fit_intercept, mode, max_iter, 1e-10, 1e-6, path, 0,
+                       noisy_rpc=rows_per_chunk)["theta"]
+    out, prev, last_step = [], tr["start"], None
+    for i, r in enumerate(tr["rec"]):
+        th = tr["theta"][i]
+        e = {"theta": th, "s": float(np.abs(th - prev).max()), "rec": r, "carried": 0.0}
+        if carried is not None and i < len(carried):
+            e["carried"] = float(np.abs(carried[i] - th).max())
+        if r["halved"]:
+            e["D"] = last_step["D"] * 2.0 ** -r["bt"]
+            e["budget"] = last_step["budget"] * 2.0 ** -r["bt"]
+            e["noise"] = last_step["noise"] * 2.0 ** -r["bt"]
+        else:
+            eta = D.Z @ prev
+            mu, w = weights(family, eta)
+            g = D.Z.T @ (y - mu)
+            hm = r["hmode"]
+            d = th - prev
+            H_def = hessian(D, w, hm, drop_last=True)
+            e["D"] = float(np.abs(np.linalg.solve(H_def, g) - d).max())
+            e["budget"] = e["noise"] = 0.0
+            if hm != "fp64":
+                e["budget"] = float(np.abs(np.linalg.solve(hessian(D, w, "fp64"), g) - d).max())
+                Hn = noisy_hessian(D, w, hm, rows_per_chunk)
+                e["noise"] = float(np.abs(np.linalg.solve(Hn, g) - d).max())
+            last_step = e
+        out.append(e)
+        prev = th
+    return out, tr
+
+
+# --------------------------------------------------------------------------
+# the cases of tests/test_gpu_newton_steps.py
+# --------------------------------------------------------------------------
+# Partition sizes: every n_k <= max(2048, 64 P), so the warm-start row-prefix
+# level would stream more than half of the rows and is skipped (fit_plan.hpp
+# level_plans / wide_level_plans), and n_k >= 10 P.  Ragged: no multiple of
+# 32; 3001 % 32 = 25, 1500 % 32 = 28, 2047 % 32 = 31, 777 % 32 = 9 and 772 %
+# 32 = 4 (a block tail under 8 rows); 777 < rows_per_chunk (one chunk), the
+# others 2-4 chunks of uneven length.
+RPC = 1000
+SIZES_SMALL = (2047, 1500, 772, 1999)     # P <= 32: the cap is 2048
+SIZES_77 = (3001, 1500, 2047, 777)        # 33 <= P <= 77 (3001 where 64 P allows it)
+SIZES_MID = (3001, 1500, 2047, 1300)      # 78 <= P <= 130 (1300 % 32 = 20)
+SIZES_BIG = (3001, 2047, 4099, 1996)      # P up to 193 (1996 % 32 = 12, 4099 % 32 = 3)
+
+
+def sizes_for(P):
+    if P <= 32:
+        return SIZES_SMALL
+    if P <= 77:
+        return tuple(s for s in SIZES_77 if s <= max(2048, 64 * P))
+    if P <= 130:
+        return SIZES_MID
+    return SIZES_BIG
+
+
+def wide_sizes(P):
+    """Two partitions, 10 P <= n_k <= 64 P, ragged."""
+    return (10 * P + 1211, 12 * P + 5)
+
+
+# (p, fit_intercept, standardised)
+LOGISTIC_MIXED = [(1, False, False), (15, True, False), (17, False, False), (33, False, True),
+                  (100, True, False), (112, False, False), (113, False, False),
+                  (127, True, True), (129, False, False), (191, True, False)]
+LOGISTIC_F32 = [(17, False, False), (100, True, True), (129, False, False)]
+LOGISTIC_FP64 = [(33, False, False), (129, False, False)]
+POISSON_MIXED = [(1, True, False), (16, False, False), (33, False, True), (64, True, False),
+                 (100, True, False), (129, False, False), (192, False, False)]
+POISSON_F32 = [(33, False, False), (129, False, False)]
+POISSON_FP64 = [(100, True, False)]
+WIDE_MIXED = [(193, False, False), (256, False, False), (300, True, True), (385, False, False)]
+WIDE_FP64 = [(210, False, False)]
+
+FUSED_CASES = ([("logistic", "mixed") + c for c in LOGISTIC_MIXED] +
+               [("logistic", "mixed_f32") + c for c in LOGISTIC_F32] +
+               [("logistic", "fp64") + c for c in LOGISTIC_FP64] +
+               [("poisson", "mixed") + c for c in POISSON_MIXED] +
+               [("poisson", "mixed_f32") + c for c in POISSON_F32] +
+               [("poisson", "fp64") + c for c in POISSON_FP64])
+WIDE_CASES = ([("logistic", "mixed") + c for c in WIDE_MIXED] +
+              [("logistic", "fp64") + c for c in WIDE_FP64])
+ITERS = (1, 2, 3)
+
+
+def case_id(c):
+    fam, mode, p, fi, std = c
+    return f"{fam}-{mode}-p{p}-{'icpt' if fi else 'noicpt'}{'-std' if std else ''}"
+
+
+def poisson_beta(p):
+    """True coefficient of the Poisson cases: eta = beta * (sum of
+    max(1, floor(0.4 p)) U(-1/2, 1/2) columns) keeps sd(eta) ~ 0.35 at every
+    p, so no Newton step from the start point overshoots (checked on the CPU:
+    no halving, by the margin)."""
+    return min(0.5, 0.35 / np.sqrt(max(1, int(0.4 * p)) / 12.0))
+
+
+# Seeds of the shapes whose default seed (1000 + 7 p + intercept) breaks a
+# condition of tests/test_cpu_newton_ref.py (a decision within a factor 10 of
+# its threshold, or a last row with so little leverage that the modelled
+# rounding is not 100 times below the one-row defect): the next seeds were
+# tried in order.  Chosen from the emulator alone.
+SEEDS = {("logistic", 1, False, False): 1082, ("poisson", 1, True, False): 1010,
+         ("poisson", 33, False, False): 1232}
+
+
+@functools.lru_cache(maxsize=None)
+def case_data(fam, p, fi, std, wide=False, seed=0):
+    """(X, y, offsets, center, scale) of one shape."""
+    P = p + int(fi)
+    sizes = wide_sizes(P) if wide else sizes_for(P)
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    n = int(off[-1])
+    seed = seed or SEEDS.get((fam, p, fi, std), 1000 + 7 * p + int(fi))
+    center = scale = None
+    b = np.zeros(p)
+    b[:max(1, int(0.4 * p))] = poisson_beta(p)
+    if fam == "poisson" and not std:
+        X, y = R.simulate(n, p, seed, fit_intercept=fi, theta_true=b)
+    else:
+        X, y = O.simulate_counter(n, p, seed)
+        X = np.ascontiguousarray(X)
+    if std:  # columns worth standardising
+        X = X * np.linspace(0.5, 3.0, p) + np.linspace(-1.0, 2.0, p)
+        center, scale = X.mean(0), X.std(0, ddof=1)
+        if fam == "poisson":  # the simulator's y, on columns of the generator's spread
+            eta = ((X - center) / scale * np.sqrt(1.0 / 12.0)) @ b + (1.0 if fi else 0.0)
+            y = np.random.default_rng(seed).poisson(np.exp(eta)).astype(np.float64)
+    return X, y, off, center, scale
+
+
+@functools.lru_cache(maxsize=None)
+def case_yardsticks(fam, mode, p, fi, std, wide=False):
+    """Per partition: (step_yardsticks list, trajectory) at max_iter = 3."""
+    X, y, off, center, scale = case_data(fam, p, fi, std, wide)
+    path = "wide" if wide else "fused"
+    out = []
+    for a, b in zip(off[:-1], off[1:]):
+        D = Design(X[a:b], fi, center, scale, path)
+        out.append(step_yardsticks(D, y[a:b], fam, fi, mode, max(ITERS), RPC, path))
+    return out
+
+
+# ---- categorical: q = 3 numeric columns, factors of 4 and 6 levels ----------
+CAT_LEVELS = (4, 6)
+CAT_SIZES = (2047, 1500, 777)  # P = 12: the cap is 2048
+CAT_ITERS = (1, 2)
+
+
+@functools.lru_cache(maxsize=None)
+def cat_data(seed=5):
+    """(Xn, codes uint8, y, levels, offsets, dense dummy design)."""
+    rng = np.random.default_rng(seed)
+    n, q = sum(CAT_SIZES), 3
+    Xn = rng.random((n, q)) - 0.5
+    codes = np.stack([np.minimum((L * rng.random(n) ** 2).astype(np.int64), L - 1)
+                      for L in CAT_LEVELS], axis=1).astype(np.uint8)
+    levels = np.asarray(CAT_LEVELS, dtype=np.int32)
+    Xd = O.expand_codes(Xn, codes, levels)
+    beta = np.concatenate([rng.random(q) * 2 - 1, 0.3 * rng.standard_normal(Xd.shape[1] - q)])
+    prob = 1.0 / (1.0 + np.exp(-(Xd @ beta - 0.3)))
+    y = (rng.random(n) < prob).astype(np.float64)
+    off = np.concatenate([[0], np.cumsum(CAT_SIZES)]).astype(np.int64)
+    return Xn, codes, y, levels, off, Xd
+
+
+# ---- halving: the no-intercept overshoot case of test_gpu_poisson ----------
+HALVING_ITERS = (1, 2, 3, 4, 5)
+HALVING_N = 8000
+
+
+@functools.lru_cache(maxsize=None)
+def halving_data():
+    """test_gpu_poisson.test_overshoot[False]: mean y ~ 39, start theta = 0.
+    The 8000 rows are cut into K = 4 partitions of 2000 (<= 2048, so no
+    warm-start level; every one of them overshoots the same way).
+    test_cpu_newton_ref also pins the emulator against _poisson_ref.fit on all
+    8000 rows as one partition."""
+    th = np.zeros(10)
+    th[0] = 1.2
+    X, y = R.simulate(HALVING_N, 10, seed=11, shift0=3.0, theta_true=th)
+    off = np.arange(5, dtype=np.int64) * 2000
+    return X, y, off
+
+
+# ---- to convergence: no escalation on a clean design -------------------------
+# (case, seed, tol, switch_tol).  tol sits between the first exact step of a
+# bf16-steered fit (~1e-9 .. 1e-12: the last bf16 step times the bf16
+# contraction rate) and the second (~1e-16, rounding): with the default 1e-10
+# the decision at the first would be a coin flip.  Poisson: the fourth step of
+# every partition of this shape lands within a factor 10 of the default
+# switch_tol (1 + max |theta|), so the run uses 1e-7.  The seeds are the first
+# at which every decision of every partition clears its threshold by 10.
+CONVERGED = [(("logistic", "mixed", 100, True, False), 5024, 1e-13, 1e-6),
+             (("poisson", "mixed", 64, True, False), 5007, 1e-14, 1e-7)]
+
+
+# ---- K > 256 -----------------------------------------------------------------
+MANY_K, MANY_N, MANY_P = 300, 400, 5
+MANY_RPC = 150  # three chunks per partition: the partial sums run
+MANY_SAMPLE = (0, 1, 77, 255, 256, 257, 298, 299)
+
+
+@functools.lru_cache(maxsize=None)
+def many_data():
+    X, y = R.simulate(MANY_K * MANY_N, MANY_P, seed=17, fit_intercept=True)
+    off = np.arange(MANY_K + 1, dtype=np.int64) * MANY_N
+    return X, y, off
