@@ -96,6 +96,13 @@ SIGNATURES = {
          ctypes.POINTER(FitOptions), _P]),
     "dlsa_poisson_loglik_batched_sum": (
         ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
+    # the Poisson entries with eta_offset [n] inserted after y
+    "dlsa_poisson_fit_batched_offset": (
+        ctypes.c_int,
+        [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _F64, _P, _P, _P, _P, _P, _P,
+         ctypes.POINTER(FitOptions), _P]),
+    "dlsa_poisson_loglik_batched_sum_offset": (
+        ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
     "dlsa_ols_fit_batched": (
         ctypes.c_int,
         [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(FitOptions),

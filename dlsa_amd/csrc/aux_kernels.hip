@@ -122,10 +122,72 @@ __global__ __launch_bounds__(256) void poisson_start_kernel(const double* y, con
   }
 }
 
+// The start point with a per-row offset o (eta = x . theta + o): the same
+// fixed-order pass also sums exp(o) and checks o.  With an intercept the fit
+// starts at theta = (log(sum y / sum exp(o)), 0, ..., 0), the MLE of the
+// intercept-only rate model; without one at 0.  A non-finite o, or a sum
+// exp(o) that is not finite and positive (no finite start exists), ends the
+// partition NONFINITE like a bad y.
+__global__ __launch_bounds__(256) void poisson_start_ofs_kernel(
+    const double* y, const double* eta_offset, const int64_t* offsets, int P, int intercept,
+    double* theta, double* theta0, int32_t* phase, int32_t* status) {
+  __shared__ double ssum[4], sexp[4], smin[4];
+  __shared__ int sbad[4];
+  const int k = blockIdx.x;
+  const int64_t r0 = offsets[k], r1 = offsets[k + 1];
+  double sum = 0.0, se = 0.0, mn = INFINITY;
+  int bad = 0;
+  for (int64_t i = r0 + threadIdx.x; i < r1; i += 256) {
+    const double v = y[i], o = eta_offset[i];
+    bad |= !isfinite(v) | !isfinite(o);
+    sum += v;
+    se += exp(o);
+    mn = fmin(mn, v);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sum += __shfl_xor(sum, o);
+    se += __shfl_xor(se, o);
+    mn = fmin(mn, __shfl_xor(mn, o));
+    bad |= __shfl_xor(bad, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    ssum[threadIdx.x >> 6] = sum;
+    sexp[threadIdx.x >> 6] = se;
+    smin[threadIdx.x >> 6] = mn;
+    sbad[threadIdx.x >> 6] = bad;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  sum = ((ssum[0] + ssum[1]) + ssum[2]) + ssum[3];
+  se = ((sexp[0] + sexp[1]) + sexp[2]) + sexp[3];
+  mn = fmin(fmin(smin[0], smin[1]), fmin(smin[2], smin[3]));
+  bad = sbad[0] | sbad[1] | sbad[2] | sbad[3];
+  theta0[k] = 0.0;
+  if (r1 <= r0) return;  // empty: fit_init's DLSA_STATUS_EMPTY stands
+  if (bad || !(mn >= 0.0) || !isfinite(sum) || !isfinite(se) || !(se > 0.0) ||
+      !isfinite(sum / se)) {
+    status[k] = DLSA_STATUS_NONFINITE;
+    phase[k] = PHASE_DONE;
+  } else if (!(sum > 0.0)) {
+    status[k] = DLSA_STATUS_SINGULAR;
+    phase[k] = PHASE_DONE;
+  } else if (intercept) {
+    const double t0 = log(sum / se);
+    theta0[k] = t0;
+    theta[(int64_t)k * P] = t0;
+  }
+}
+
 hipError_t launch_poisson_start(const double* y, const int64_t* offsets_dev, int K, int P,
                                 int intercept, double* theta, double* theta0, int32_t* phase,
-                                int32_t* status, hipStream_t s) {
+                                int32_t* status, hipStream_t s, const double* eta_offset) {
   if (K <= 0) return hipSuccess;
+  if (eta_offset) {
+    hipLaunchKernelGGL(poisson_start_ofs_kernel, dim3(K), dim3(256), 0, s, y, eta_offset,
+                       offsets_dev, P, intercept, theta, theta0, phase, status);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(poisson_start_kernel, dim3(K), dim3(256), 0, s, y, offsets_dev, P, intercept,
                      theta, theta0, phase, status);
   return hipGetLastError();

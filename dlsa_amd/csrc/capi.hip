@@ -32,9 +32,10 @@ hipError_t ensure_max_lds(const void* kernel, int bytes) {
 static int fit_dense(int family, const double* X, const double* y, const int64_t* offsets,
                      int32_t K, int32_t p, int32_t fit_intercept, const double* center,
                      const double* scale, int32_t max_iter, double tol, const FitOutputs& out,
-                     const dlsa_fit_options* opt_in, void* stream) {
+                     const dlsa_fit_options* opt_in, void* stream,
+                     const double* eta_offset = nullptr) {
   DenseFit f{family, X, y, offsets, K, p, fit_intercept, center, scale, max_iter, tol, out,
-             fit_begin(opt_in, stream)};
+             fit_begin(opt_in, stream), eta_offset};
   int rc = check_offsets(offsets, K);
   if (rc != DLSA_OK) return rc;
   if (p < 0 || (p == 0 && !fit_intercept)) {
@@ -139,6 +140,18 @@ int dlsa_poisson_fit_batched_ex(const double* X, const double* y, const int64_t*
                    tol, {theta, sig_inv, sig_inv_theta, loglik, iters, status}, opt, stream);
 }
 
+int dlsa_poisson_fit_batched_offset(const double* X, const double* y, const double* eta_offset,
+                                    const int64_t* offsets, int32_t K, int32_t p,
+                                    int32_t fit_intercept, const double* center,
+                                    const double* scale, int32_t max_iter, double tol,
+                                    double* theta, double* sig_inv, double* sig_inv_theta,
+                                    double* loglik, int32_t* iters, int32_t* status,
+                                    const dlsa_fit_options* opt, void* stream) {
+  return fit_dense(FAMILY_POISSON, X, y, offsets, K, p, fit_intercept, center, scale, max_iter,
+                   tol, {theta, sig_inv, sig_inv_theta, loglik, iters, status}, opt, stream,
+                   eta_offset);
+}
+
 int dlsa_logistic_fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
                                   const int64_t* offsets, int32_t K, int32_t q, int32_t F,
                                   const int32_t* levels, int32_t fit_intercept,
@@ -186,7 +199,8 @@ int dlsa_logistic_fit_batched(const double* X, const double* y, const int64_t* o
 static int loglik_dense(int family, const double* X, const double* y, const int64_t* offsets, int32_t K,
                         int32_t p, int32_t fit_intercept, const double* center,
                         const double* scale, const double* betas, int32_t n_beta,
-                        double* loglik, double* loglik_sum, void* stream_) {
+                        double* loglik, double* loglik_sum, void* stream_,
+                        const double* eta_offset = nullptr) {
   g_last_error.clear();
   hipStream_t stream = (hipStream_t)stream_;
   int rc = check_offsets(offsets, K);
@@ -234,11 +248,13 @@ static int loglik_dense(int family, const double* X, const double* y, const int6
     const uintptr_t xend = (uintptr_t)(X + n_total * (int64_t)p);
     ea.x_last16 = ((xend + 15) & ~(uintptr_t)15) - 16;
     ea.y_last4 = (uintptr_t)(y + n_total) - 4;
+    ea.eta_offset = eta_offset;
+    if (eta_offset) ea.o_last4 = (uintptr_t)(eta_offset + n_total) - 4;
     ea.p = p;
     ea.P = P;
     ea.intercept = fit_intercept ? 1 : 0;
     ea.nbeta = n_beta;
-    ea.slot_bytes = eval_slot_bytes(p);
+    ea.slot_bytes = eval_slot_bytes(p, eta_offset != nullptr);
     const int PM = ((P + 7) / 8) * 8;
     const int budget = 160 * 1024 - (n_beta * PM + 2 * PM + 64) * 8;
     ea.nslot = std::max(2, std::min(budget / ea.slot_bytes, 6));
@@ -275,6 +291,16 @@ int dlsa_poisson_loglik_batched_sum(const double* X, const double* y, const int6
                                     double* loglik_sum, void* stream) {
   return loglik_dense(FAMILY_POISSON, X, y, offsets, K, p, fit_intercept, center, scale, betas,
                       n_beta, loglik, loglik_sum, stream);
+}
+
+int dlsa_poisson_loglik_batched_sum_offset(const double* X, const double* y,
+                                           const double* eta_offset, const int64_t* offsets,
+                                           int32_t K, int32_t p, int32_t fit_intercept,
+                                           const double* center, const double* scale,
+                                           const double* betas, int32_t n_beta, double* loglik,
+                                           double* loglik_sum, void* stream) {
+  return loglik_dense(FAMILY_POISSON, X, y, offsets, K, p, fit_intercept, center, scale, betas,
+                      n_beta, loglik, loglik_sum, stream, eta_offset);
 }
 
 int dlsa_logistic_loglik_categorical(const double* Xn, const uint8_t* codes, const double* y,

@@ -95,6 +95,26 @@ struct PassArgs {
   // is added where loglik is published (newton_solve.hip)
   double* slab_llc;
 };
+// PassArgs of the cooperative and per-wave passes with the Poisson family's
+// per-row offset: eta = x . theta + eta_offset.  The offset streams like y (a
+// bounds-checked buffer resource of its own over the chunk, placed behind y
+// in the ring slot).  Only the OFS instantiations take this struct as their
+// kernel argument: growing PassArgs itself moved the register allocation of
+// a dozen offset-free cooperative kernels (NT = 4, 9: up to +20 VGPRs), so
+// every other kernel keeps the PassArgs it had.  The dispatchers
+// (launch_irls_coop, launch_irls_wave) route on eta_offset != nullptr.
+struct PassArgsOfs : PassArgs {
+  const double* eta_offset;  // [n_total] or null (none)
+  uintptr_t o_last4;         // last 4-B address inside eta_offset
+};
+template <bool OFS>
+struct pass_args_of {
+  typedef PassArgs type;
+};
+template <>
+struct pass_args_of<true> {
+  typedef PassArgsOfs type;
+};
 
 // A/B knobs of profiling builds.  The product library reads no environment
 // variable that changes a result (include/dlsa_hip.h): env_knob() is getenv
@@ -229,6 +249,9 @@ struct EvalArgs {
   uintptr_t y_last4;
   int32_t p, P, intercept, nbeta;
   int32_t nslot, slot_bytes;
+  // FAMILY_POISSON: per-row offset added to every candidate's eta (null: none)
+  const double* eta_offset;
+  uintptr_t o_last4;
 };
 
 // Wide-P path (DLSA_MAX_P_FUSED < P <= DLSA_MAX_P, wide_exact.hip): a row
@@ -392,10 +415,10 @@ int wide_newton_lds_bytes(int NB);
 hipError_t launch_loglik_eval(const EvalArgs& a, int family, int n_chunks, hipStream_t s);
 hipError_t launch_loglik_reduce(const double* partial, const int32_t* pcb, int K, int B,
                                 double* out, hipStream_t s);
-int eval_slot_bytes(int p);
+int eval_slot_bytes(int p, bool eta_offset = false);  // + the offset's 256 B behind y
 // per-wave fp64 pass (irls_wave_impl.hpp): P <= 128
-hipError_t launch_irls_wave(const PassArgs& a, int NT, bool standardize, int family, int n_chunks,
-                            hipStream_t s);
+hipError_t launch_irls_wave(const PassArgsOfs& a, int NT, bool standardize, int family,
+                            int n_chunks, hipStream_t s);
 int wave_lds_bytes(int NT, int p);
 constexpr int kWaveMaxNT = 8;
 // Ozaki-scheme exact pass (irls_oz_impl.hpp): NT <= kOzMaxNT, chunks <= kOzMaxRows rows;
@@ -410,9 +433,9 @@ constexpr int kOzMaxNT = 7;
 bool ols_stream_applies(int NT);
 hipError_t launch_ols_stream(const PassArgs& a, int NT, bool standardize, int n_chunks,
                              hipStream_t s);
-hipError_t launch_irls_coop(const PassArgs& a, int NT, int prec, bool standardize, int family,
+hipError_t launch_irls_coop(const PassArgsOfs& a, int NT, int prec, bool standardize, int family,
                             int n_chunks, hipStream_t s);
-int coop_slot_bytes(int NT, int p);
+int coop_slot_bytes(int NT, int p, bool eta_offset = false);  // + the offset's 256 B behind y
 int coop_extra_bytes(int NT);  // LDS beyond the ring
 hipError_t launch_newton_solve(const SolveArgs& a, int K, hipStream_t s);
 hipError_t launch_fit_init(const int64_t* offsets_dev, int K, int P, int start_phase,
@@ -425,10 +448,13 @@ hipError_t launch_level_reset(int K, int P, int start_phase, int32_t* phase, int
 // Poisson start point (aux_kernels.hip): per partition one fixed-order pass
 // over y; theta0[k] = log(mean y) (intercept) or 0, written to theta[k][0]; a
 // negative or non-finite y ends the partition NONFINITE, sum y = 0 SINGULAR
-// (phase PHASE_DONE, outputs left zeroed by fit_init)
+// (phase PHASE_DONE, outputs left zeroed by fit_init).  With eta_offset the
+// same pass sums exp(o): theta0[k] = log(sum y / sum exp(o)), and a non-finite
+// o or sum exp(o) ends the partition NONFINITE too
 hipError_t launch_poisson_start(const double* y, const int64_t* offsets_dev, int K, int P,
                                 int intercept, double* theta, double* theta0, int32_t* phase,
-                                int32_t* status, hipStream_t s);
+                                int32_t* status, hipStream_t s,
+                                const double* eta_offset = nullptr);
 hipError_t launch_polish_mark(int K, int32_t* phase, const int32_t* status, int32_t* counters,
                               hipStream_t s);
 // theta_rec[k] = theta[k] for the partitions in phase `ph` (before a pass

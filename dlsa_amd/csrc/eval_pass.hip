@@ -54,15 +54,20 @@ __host__ __device__ __forceinline__ int ev_npieces(int p) {
 
 }  // namespace
 
-int eval_slot_bytes(int p) {
+// (eta_offset: the rows' offsets, ERB doubles behind y)
+int eval_slot_bytes(int p, bool eta_offset) {
   const int d = (ev_npieces(p) + EW - 1) / EW;
-  return 16 + d * EW * 1024 + ((p + 8) / 8) * 8 * 8 + ERB * 8;
+  return 16 + d * EW * 1024 + ((p + 8) / 8) * 8 * 8 + ERB * 8 + (eta_offset ? ERB * 8 : 0);
 }
 
 // FAM: FAMILY_LOGISTIC, or FAMILY_POISSON (y eta - exp(eta) - lgamma(y + 1), the
-// full log-likelihood; the constant once per row, not per candidate)
-template <int FAM>
+// full log-likelihood; the constant once per row, not per candidate).
+// OFS (FAMILY_POISSON only): a.eta_offset[row] is added to every candidate's
+// eta; it streams like y, one more load per wave and block.
+template <int FAM, bool OFS = false>
 __global__ __launch_bounds__(256) void loglik_eval_kernel(const EvalArgs a) {
+  static_assert(!OFS || FAM == FAMILY_POISSON, "the offset is the Poisson family's");
+  constexpr int NLD = 1 + (OFS ? 1 : 0);  // loads per block beside X: y (and the offset)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int chunk = blockIdx.x;
   const int part = a.chunk_part[chunk];
@@ -111,6 +116,12 @@ __global__ __launch_bounds__(256) void loglik_eval_kernel(const EvalArgs a) {
     uintptr_t ys = (uintptr_t)(a.y + row0 + (int64_t)bb * ERB) + (uintptr_t)lane * 4;
     ys = ys < a.y_last4 ? ys : a.y_last4;
     __builtin_amdgcn_global_load_lds((gbl_void_t*)ys, (lds_void_t*)(sbase + slot_x), 4, 0, 0);
+    if constexpr (OFS) {
+      uintptr_t os = (uintptr_t)(a.eta_offset + row0 + (int64_t)bb * ERB) + (uintptr_t)lane * 4;
+      os = os < a.o_last4 ? os : a.o_last4;
+      __builtin_amdgcn_global_load_lds((gbl_void_t*)os, (lds_void_t*)(sbase + slot_x + ERB * 8),
+                                       4, 0, 0);
+    }
   };
 
   const int sl = lane & 7;
@@ -120,7 +131,9 @@ __global__ __launch_bounds__(256) void loglik_eval_kernel(const EvalArgs a) {
   for (int b = 0; b < EMAXB; ++b) llacc[b] = 0.0;
 
   for (int b = 0; b < nslot - 1; ++b) issue(b);
-  const int keep = (nslot - 2) * (d + 1);
+  // d + NLD loads per wave and block; nslot d <= 40 (the ring fits 160 KiB of
+  // 4 KiB piece rows) and nslot <= 6, so keep <= 4 (6 + 2) = 32 <= the bound
+  const int keep = (nslot - 2) * (d + NLD);
   for (int blk = 0; blk < nb; ++blk) {
     ev_wait_le<40>(keep);
     __syncthreads();
@@ -143,13 +156,16 @@ __global__ __launch_bounds__(256) void loglik_eval_kernel(const EvalArgs a) {
         if (b < B) eta[b] = fma(v, bet[b * PM + f], eta[b]);
     }
     const double yv = ys[rB];
+    [[maybe_unused]] double ov = 0.0;
+    if constexpr (OFS) ov = ys[ERB + rB];
     double lg = 0.0;  // lgamma(y + 1): 0 at y = 0 and y = 1
     if constexpr (FAM == FAMILY_POISSON)
       if (valid && sl == 0 && yv != 0.0 && yv != 1.0) lg = lgamma1p(yv);
 #pragma unroll
     for (int b = 0; b < EMAXB; ++b) {
       if (b < B) {
-        const double e = ev_red8(eta[b]);
+        double e = ev_red8(eta[b]);
+        if constexpr (OFS) e += ov;
         if constexpr (FAM == FAMILY_POISSON) {
           if (valid && sl == 0) llacc[b] += yv * e - exp(e) - lg;
         } else {
@@ -182,8 +198,10 @@ hipError_t launch_loglik_eval(const EvalArgs& a, int family, int n_chunks, hipSt
   const int PM = ((a.P + 7) / 8) * 8;
   const size_t lds = (size_t)a.nslot * a.slot_bytes +
                      ((size_t)a.nbeta * PM + 2 * PM + EW * EMAXB) * sizeof(double);
-  auto kern = family == FAMILY_POISSON ? loglik_eval_kernel<FAMILY_POISSON>
-                                       : loglik_eval_kernel<FAMILY_LOGISTIC>;
+  if (a.eta_offset && family != FAMILY_POISSON) return hipErrorInvalidValue;
+  auto kern = family != FAMILY_POISSON ? loglik_eval_kernel<FAMILY_LOGISTIC>
+              : a.eta_offset           ? loglik_eval_kernel<FAMILY_POISSON, true>
+                                       : loglik_eval_kernel<FAMILY_POISSON>;
   {
     hipError_t e = ensure_max_lds((const void*)kern, 160 * 1024);
     if (e != hipSuccess) return e;

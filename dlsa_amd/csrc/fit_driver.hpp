@@ -284,6 +284,8 @@ struct DenseFit {
   double tol;
   FitOutputs out;
   FitStart start;
+  // FAMILY_POISSON: per-row offset of eta [n_total], device, or null (fused path only)
+  const double* eta_offset = nullptr;
 };
 int fit_fused(const DenseFit& f);  // P <= DLSA_MAX_P_FUSED (fit_fused.hip)
 int fit_wide(const DenseFit& f);   // P > DLSA_MAX_P_FUSED (fit_wide.hip)

@@ -22,7 +22,7 @@ struct FusedFit {
   StreamTimer timed;
   Readback h;
   int32_t* h_route = nullptr;  // [K] phases with stale partitions marked (one launch)
-  PassArgs pa;
+  PassArgsOfs pa;  // (eta_offset null unless the fit has a per-row offset)
   SolveArgs sa;
   int approx_prec = PREC_BF16;
   bool standardize = false;
@@ -83,7 +83,9 @@ void FusedFit::set_pass_args(const Plan& pl, const Workspace& ws, const Layout& 
     const uintptr_t xend = (uintptr_t)(f.X + n_total * (int64_t)f.p);
     pa.x_last16 = ((xend + 15) & ~(uintptr_t)15) - 16;
     pa.y_last4 = (uintptr_t)(f.y + n_total) - 4;
+    if (f.eta_offset) pa.o_last4 = (uintptr_t)(f.eta_offset + n_total) - 4;
   }
+  pa.eta_offset = f.eta_offset;
   pa.p = f.p;
   pa.P = P;
   pa.intercept = f.fit_intercept ? 1 : 0;
@@ -92,7 +94,7 @@ void FusedFit::set_pass_args(const Plan& pl, const Workspace& ws, const Layout& 
   // row phase and barrier waits overlap the other's tile phase (measured
   // 27.4 -> 21.8 ms per bf16 pass at config 2 against one workgroup with a
   // deeper ring)
-  pa.slot_bytes = coop_slot_bytes(pl.NT, f.p);
+  pa.slot_bytes = coop_slot_bytes(pl.NT, f.p, f.eta_offset != nullptr);
   const int wg_per_cu = pl.NT < 8 ? 2 : 1;
   const int budget = 160 * 1024 / wg_per_cu - coop_extra_bytes(pl.NT);
   pa.nslot = std::max(2, std::min(budget / pa.slot_bytes, 6));
@@ -135,14 +137,14 @@ hipError_t FusedFit::pass(int ph, const Plan& q, bool full, const std::vector<in
     if (e != hipSuccess) return e;
   }
   hipError_t e = timed(f64 ? &g_stats.ms_pass_fp64 : &g_stats.ms_pass_fp32, [&] {
-    PassArgs pc = pa;
+    PassArgsOfs pc = pa;
     pc.colmax = (oz || rec_x) ? d_colmax : nullptr;
     pc.zcolmax = (oz || rec_z) ? d_zcolmax : nullptr;
     pc.theta_rec = d_threc;
     if (oz) {
       hipError_t eo = launch_irls_oz(pc, q.NT, standardize, family, q.n_chunks, stream);
       if (eo != hipSuccess || !split) return eo;
-      PassArgs ps = pa;  // the stale partitions on the fp64 MFMA
+      PassArgsOfs ps = pa;  // the stale partitions on the fp64 MFMA
       ps.want_phase = PHASE_F64_STALE;
       return launch_irls_wave(ps, q.NT, standardize, family, q.n_chunks, stream);
     }
@@ -193,7 +195,7 @@ hipError_t FusedFit::spec_pass(const Plan& q, bool full) {
     if (e != hipSuccess) return e;
   }
   return timed(&g_stats.ms_pass_fp32, [&] {
-    PassArgs pc = pa;
+    PassArgsOfs pc = pa;
     pc.colmax = nullptr;
     pc.zcolmax = zg ? d_zcolmax : nullptr;
     pc.theta_rec = d_threc;
@@ -268,7 +270,8 @@ int FusedFit::run() {
   DLSA_HIP_TRY(fit_init(sa, d_offsets, K, start_phase, stream));
   if (family == FAMILY_POISSON)  // the start point; ends the partitions that have no MLE
     DLSA_HIP_TRY(launch_poisson_start(f.y, d_offsets, K, P, f.fit_intercept ? 1 : 0, sa.theta,
-                                      const_cast<double*>(sa.theta0), sa.phase, sa.status, stream));
+                                      const_cast<double*>(sa.theta0), sa.phase, sa.status, stream,
+                                      f.eta_offset));
   int n_running[kRunPhases] = {0, 0, 0};
   for (int k = 0; k < K; ++k)
     if (offsets[k + 1] > offsets[k]) n_running[start_phase]++;

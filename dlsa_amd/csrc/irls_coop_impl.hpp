@@ -162,8 +162,9 @@ constexpr int coop_waves(int NT) { return NT > 8 ? 8 : 4; }
 // A slot holds exactly the block's pieces: a wave's surplus issues (the piece
 // count is rounded up to the wave count so that every wave waits on the same
 // vmcnt) re-load the last piece onto itself.
-inline int coop_slot_bytes_impl(int NT, int p) {
-  return 16 + npieces_for(p) * 1024 + 16 * NT * 8 + RB * 8;
+// With a per-row offset (Poisson, OFS) its RB doubles follow y.
+inline int coop_slot_bytes_impl(int NT, int p, bool eta_offset = false) {
+  return 16 + npieces_for(p) * 1024 + 16 * NT * 8 + RB * 8 + (eta_offset ? RB * 8 : 0);
 }
 
 // LDS beyond the ring: w, r of the block [2][RB] fp64, center / 1/scale
@@ -246,14 +247,18 @@ __device__ __forceinline__ void store_tiles(Acc (&acc)[(CG<NT, W>::TPW)], double
 // value of the bf16 image) into a.zcolmax (2: the bf16 passes of partitions
 // near convergence); the Ozaki exact pass takes its digit scales from the
 // last records (irls_oz_impl.hpp)
-template <int NT, int W, int PREC, bool STD, int FAM, int CM = 0>
+// OFS (FAMILY_POISSON only): eta = x . theta + a.eta_offset[row]; the offset
+// streams like y, one more DMA piece of RB * 8 bytes per block behind y
+template <int NT, int W, int PREC, bool STD, int FAM, int CM = 0, bool OFS = false>
 __global__ __launch_bounds__(64 * W, (W == 8 || NT < 8) ? 2 : 1)
-void irls_coop_kernel(const PassArgs a) {
+void irls_coop_kernel(const typename pass_args_of<OFS>::type a) {
   using G = CG<NT, W>;
   using Acc = typename std::conditional<PREC == PREC_F64, d4, f4>::type;
   constexpr int RPW = G::RPW, LPR = G::LPR;
   constexpr int M = G::M;
-  constexpr int MAXW = 4 * (G::MAX_D + 1);  // nslot <= 6
+  static_assert(!OFS || FAM == FAMILY_POISSON, "the offset is the Poisson family's");
+  constexpr int NLD = 1 + (OFS ? 1 : 0);          // loads per block beside X: y (and the offset)
+  constexpr int MAXW = 4 * (G::MAX_D + NLD);  // nslot <= 6
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int chunk = blockIdx.x;
@@ -273,7 +278,7 @@ void irls_coop_kernel(const PassArgs a) {
   const int slot_bytes = a.slot_bytes;
   const int npieces = npieces_for(p);
   const int d = (npieces + W - 1) / W;
-  const int slot_x = G::PAD + npieces * 1024 + G::PMAX * 8;  // y follows
+  const int slot_x = G::PAD + npieces * 1024 + G::PMAX * 8;  // y follows (then the offset)
   double* wr = (double*)(smem + nslot * slot_bytes);       // [2][RB]: w, r of the block
   double* stdv = wr + 2 * RB;  // [2][PMAX]: center, 1/scale by feature (STD only)
   __bf16* obx = (__bf16*)(stdv + 2 * G::PMAX);  // [2][PMAX][OBS] bf16 operands (PREC_BF16)
@@ -349,6 +354,11 @@ void irls_coop_kernel(const PassArgs a) {
   const uintptr_t ycb = (uintptr_t)(a.y + row0);
   const __amdgpu_buffer_rsrc_t yr_rsrc = uniform_rsrc(ycb, a.y_last4 + 4 - ycb);
   const int vx = lane * 16, vy = lane * 4;
+  [[maybe_unused]] __amdgpu_buffer_rsrc_t or_rsrc;
+  if constexpr (OFS) {
+    const uintptr_t ocb = (uintptr_t)(a.eta_offset + row0);
+    or_rsrc = uniform_rsrc(ocb, a.o_last4 + 4 - ocb);
+  }
   auto issue = [&](int blk) {
     const int bb = blk < nb ? blk : nb - 1;  // tail: harmless re-fetch, fixed counts
     char* sbase = smem + (blk % nslot) * slot_bytes;
@@ -363,10 +373,16 @@ void irls_coop_kernel(const PassArgs a) {
     }
     __builtin_amdgcn_raw_ptr_buffer_load_lds(yr_rsrc, (lds_void_t*)(sbase + slot_x), 4, vy,
                                              bb * RB * 8, 0, 0);
+    if constexpr (OFS)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(or_rsrc, (lds_void_t*)(sbase + slot_x + RB * 8), 4,
+                                               vy, bb * RB * 8, 0, 0);
   };
 
+  // every wave issues d + NLD loads per block, in block order: with at most
+  // that many per block in flight for the nslot - 2 blocks after b, every
+  // load of block b (and before) has landed
   for (int b = 0; b < nslot - 1; ++b) issue(b);
-  const int keep = (nslot - 2) * (d + 1);
+  const int keep = (nslot - 2) * (d + NLD);
 
   for (int b = 0; b < nb; ++b) {
     wait_vmcnt_le<MAXW>(keep);  // this wave's pieces of block b landed
@@ -398,7 +414,11 @@ void irls_coop_kernel(const PassArgs a) {
         else
           e0 = fma(v, beta[m], e0);
       }
-      const double e = red_row<RPW>(e0 + e1);  // bitwise-identical in all lanes of the row
+      double e = red_row<RPW>(e0 + e1);  // bitwise-identical in all lanes of the row
+      // the offset once, after the reduction (every lane of the row adds the
+      // same value); a padded row's may be the next partition's, even NaN: the
+      // selects on `valid` below keep it out of w, r and the log-likelihood
+      if constexpr (OFS) e += ys[RB + rB];
       const double yv = ys[rB];
       double w, r;
       if constexpr (FAM == FAMILY_LOGISTIC && DLSA_ABLATE == 2) {
@@ -576,9 +596,10 @@ void irls_coop_kernel(const PassArgs a) {
   }
 }
 
-template <int NT, int W, int PREC, bool STD, int FAM, int CM = 0>
-static hipError_t launch_c(const PassArgs& a, int n_chunks, hipStream_t s) {
-  auto kern = irls_coop_kernel<NT, W, PREC, STD, FAM, CM>;
+template <int NT, int W, int PREC, bool STD, int FAM, int CM = 0, bool OFS = false>
+static hipError_t launch_c(const typename pass_args_of<OFS>::type& a, int n_chunks,
+                           hipStream_t s) {
+  auto kern = irls_coop_kernel<NT, W, PREC, STD, FAM, CM, OFS>;
   const size_t lds =
       (size_t)a.nslot * a.slot_bytes + coop_extra_bytes_impl(NT);
   hipError_t e = ensure_max_lds((const void*)kern, 160 * 1024);
@@ -622,23 +643,26 @@ static hipError_t launch_coop_ntw(const PassArgs& a, int prec, bool std_, int fa
 }
 
 // Poisson family: never records digit scales (CM = 0: no int8 exact pass).
-// Instantiated by the irls_coop_pois_g*.hip units only.
-template <int NT>
-static hipError_t launch_coop_poisson_nt(const PassArgs& a, int prec, bool std_, int n_chunks,
-                                         hipStream_t s) {
+// Instantiated by the irls_coop_pois_g*.hip units only; OFS (PassArgsOfs,
+// eta_offset set) by the irls_coop_pois_ofs_g*.hip units only.
+template <int NT, bool OFS = false>
+static hipError_t launch_coop_poisson_nt(const typename pass_args_of<OFS>::type& a, int prec,
+                                         bool std_, int n_chunks, hipStream_t s) {
   constexpr int W = coop_waves(NT);
   if (a.colmax || a.zcolmax) return hipErrorInvalidValue;
+  if constexpr (OFS)
+    if (!a.eta_offset) return hipErrorInvalidValue;
   switch (prec) {
     case PREC_BF16:
-      return std_ ? launch_c<NT, W, PREC_BF16, true, FAMILY_POISSON>(a, n_chunks, s)
-                  : launch_c<NT, W, PREC_BF16, false, FAMILY_POISSON>(a, n_chunks, s);
+      return std_ ? launch_c<NT, W, PREC_BF16, true, FAMILY_POISSON, 0, OFS>(a, n_chunks, s)
+                  : launch_c<NT, W, PREC_BF16, false, FAMILY_POISSON, 0, OFS>(a, n_chunks, s);
     case PREC_F32:
-      return std_ ? launch_c<NT, W, PREC_F32, true, FAMILY_POISSON>(a, n_chunks, s)
-                  : launch_c<NT, W, PREC_F32, false, FAMILY_POISSON>(a, n_chunks, s);
+      return std_ ? launch_c<NT, W, PREC_F32, true, FAMILY_POISSON, 0, OFS>(a, n_chunks, s)
+                  : launch_c<NT, W, PREC_F32, false, FAMILY_POISSON, 0, OFS>(a, n_chunks, s);
     default:
       if (!a.slab_llc) return hipErrorInvalidValue;
-      return std_ ? launch_c<NT, W, PREC_F64, true, FAMILY_POISSON>(a, n_chunks, s)
-                  : launch_c<NT, W, PREC_F64, false, FAMILY_POISSON>(a, n_chunks, s);
+      return std_ ? launch_c<NT, W, PREC_F64, true, FAMILY_POISSON, 0, OFS>(a, n_chunks, s)
+                  : launch_c<NT, W, PREC_F64, false, FAMILY_POISSON, 0, OFS>(a, n_chunks, s);
   }
 }
 

@@ -128,16 +128,18 @@ __device__ __forceinline__ double wv_log12(double t) {
 // profiles/r04h_ols_ab.txt).
 constexpr int kWaveSlots = 2;
 // Ring slot: [16 B pad][npieces KiB of X rows][256 B: y of up to 32 rows]
+// (ofs, the Poisson pass with a per-row offset: [256 B: the rows' offsets])
 __host__ __device__ __forceinline__ int wave_npieces(int RB, int p) {
   return (RB * p * 8 + 16 + 1023) / 1024;
 }
-__host__ __device__ __forceinline__ int wave_slot_bytes_impl(int RB, int p) {
-  return 16 + wave_npieces(RB, p) * 1024 + 256;
+__host__ __device__ __forceinline__ int wave_slot_bytes_impl(int RB, int p, bool ofs = false) {
+  return 16 + wave_npieces(RB, p) * 1024 + 256 + (ofs ? 256 : 0);
 }
 // LDS of one workgroup: 2 ring slots + w of a block [RB] + theta [PMAX] +
 // center / 1/scale [2][PMAX]
-__host__ __device__ __forceinline__ int wave_lds_bytes_impl(int NT, int RB, int p) {
-  return kWaveSlots * wave_slot_bytes_impl(RB, p) + RB * 8 + 3 * 16 * NT * 8;
+__host__ __device__ __forceinline__ int wave_lds_bytes_impl(int NT, int RB, int p,
+                                                            bool ofs = false) {
+  return kWaveSlots * wave_slot_bytes_impl(RB, p, ofs) + RB * 8 + 3 * 16 * NT * 8;
 }
 
 // Waves per workgroup.  W = 2 (P <= 112): the T tiles are split over two
@@ -276,11 +278,14 @@ struct WaveCtx {
   int nrows, nb, npieces, slot_bytes, slot_y, part, chunk;
   __amdgpu_buffer_rsrc_t xr, yr;
   uintptr_t xcb;
+  __amdgpu_buffer_rsrc_t orr;  // OFS: the chunk's rows of a.eta_offset
 };
 
 // The block loop + epilogue of wave WID (a separate code path per wave: no
 // branch merges of the accumulator arrays).
-template <int NT, int NS, int W, int WID, bool STD, int FAM>
+// OFS (FAMILY_POISSON only): eta = x . theta + a.eta_offset[row], streamed
+// like y into the 256 B behind it.
+template <int NT, int NS, int W, int WID, bool STD, int FAM, bool OFS = false>
 __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, char* smem) {
   using TL = WaveTiles<NT, NS, W, WID>;
   // strip tiles (the last tile row as NS 4x4x4_4b sub-blocks)
@@ -328,6 +333,7 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
   }
 
   // DMA: wave WID issues pieces j = WID, WID + W, ...; the last wave also y
+  // (and the offset: the wait below is for all of a wave's loads)
   auto issue = [&](int blk) {
     char* sbase = smem + (blk % kWaveSlots) * cx.slot_bytes;
     const uintptr_t start = (uintptr_t)(a.X + (cx.row0 + (int64_t)blk * RB) * p);
@@ -338,6 +344,10 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
     if (WID == W - 1)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.yr, (wlds_void_t*)(sbase + cx.slot_y), 4,
                                                lane * 4, blk * RB * 8, 0, 0);
+    if constexpr (OFS)
+      if (WID == W - 1)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.orr, (wlds_void_t*)(sbase + cx.slot_y + 256),
+                                                 4, lane * 4, blk * RB * 8, 0, 0);
   };
 
   const int fl = lane & 15, q = lane >> 4;
@@ -386,7 +396,10 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
             e0 = fma(v, bm, e0);
         }
       }
-      const double e = ETA0 ? 0.0 : wv_row_sum<RW>(e0 + e1);
+      double e = ETA0 ? 0.0 : wv_row_sum<RW>(e0 + e1);
+      // the offset once, after the reduction; a padded row's (possibly the
+      // next partition's, even NaN) stays behind the selects on `valid`
+      if constexpr (OFS) e += ys[32 + row];
       const double yv = ys[row];
       double w, r;
       if constexpr (FAM == FAMILY_LOGISTIC) {
@@ -552,9 +565,10 @@ constexpr int wave_min_waves(int NT, int W, int FAM) {
   return W == 1 ? 1 : (NT <= 4 && FAM == FAMILY_GAUSSIAN ? 5 : 2);
 }
 
-template <int NT, int NS, int W, bool STD, int FAM>
+template <int NT, int NS, int W, bool STD, int FAM, bool OFS = false>
 __global__ __launch_bounds__(64 * W, wave_min_waves(NT, W, FAM)) void irls_wave_kernel(
-    const PassArgs a) {
+    const typename pass_args_of<OFS>::type a) {
+  static_assert(!OFS || FAM == FAMILY_POISSON, "the offset is the Poisson family's");
   constexpr int RB = wave_rb(NT, W, FAM);
   constexpr int PMAX = 16 * NT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -571,7 +585,7 @@ __global__ __launch_bounds__(64 * W, wave_min_waves(NT, W, FAM)) void irls_wave_
   cx.nrows = __builtin_amdgcn_readfirstlane(a.chunk_rows[cx.chunk]);
   cx.nb = (cx.nrows + RB - 1) / RB;
   cx.npieces = wave_npieces(RB, p);
-  cx.slot_bytes = wave_slot_bytes_impl(RB, p);
+  cx.slot_bytes = wave_slot_bytes_impl(RB, p, OFS);
   cx.slot_y = 16 + cx.npieces * 1024;
   double* wv = (double*)(smem + kWaveSlots * cx.slot_bytes);
   double* bet = wv + RB;
@@ -597,14 +611,18 @@ __global__ __launch_bounds__(64 * W, wave_min_waves(NT, W, FAM)) void irls_wave_
   cx.xr = uniform_rsrc(cx.xcb, a.x_last16 + 16 - cx.xcb);
   const uintptr_t ycb = (uintptr_t)(a.y + cx.row0);
   cx.yr = uniform_rsrc(ycb, a.y_last4 + 4 - ycb);
+  if constexpr (OFS) {
+    const uintptr_t ocb = (uintptr_t)(a.eta_offset + cx.row0);
+    cx.orr = uniform_rsrc(ocb, a.o_last4 + 4 - ocb);
+  }
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   if constexpr (W == 1) {
-    wave_body<NT, NS, 1, 0, STD, FAM>(a, cx, smem);
+    wave_body<NT, NS, 1, 0, STD, FAM, OFS>(a, cx, smem);
   } else {
     if (wid == 0)
-      wave_body<NT, NS, W, 0, STD, FAM>(a, cx, smem);
+      wave_body<NT, NS, W, 0, STD, FAM, OFS>(a, cx, smem);
     else
-      wave_body<NT, NS, W, 1, STD, FAM>(a, cx, smem);
+      wave_body<NT, NS, W, 1, STD, FAM, OFS>(a, cx, smem);
   }
 }
 
@@ -615,31 +633,33 @@ static inline int wave_w(int NT, int requested = 0) {
   return wave_w_default(NT);
 }
 
-template <int NT, int W, bool STD, int FAM>
-static hipError_t launch_wave_t(const PassArgs& a, int n_chunks, hipStream_t s) {
-  const size_t lds = wave_lds_bytes_impl(NT, wave_rb(NT, W, FAM), a.p);
+template <int NT, int W, bool STD, int FAM, bool OFS = false>
+static hipError_t launch_wave_t(const typename pass_args_of<OFS>::type& a, int n_chunks,
+                                hipStream_t s) {
+  const size_t lds = wave_lds_bytes_impl(NT, wave_rb(NT, W, FAM), a.p, OFS);
   switch (wave_strip_ns(NT, a.P)) {
     case 1:
-      hipLaunchKernelGGL((irls_wave_kernel<NT, 1, W, STD, FAM>), dim3(n_chunks), dim3(64 * W), lds,
+      hipLaunchKernelGGL((irls_wave_kernel<NT, 1, W, STD, FAM, OFS>), dim3(n_chunks), dim3(64 * W), lds,
                          s, a);
       break;
     case 2:
-      hipLaunchKernelGGL((irls_wave_kernel<NT, 2, W, STD, FAM>), dim3(n_chunks), dim3(64 * W), lds,
+      hipLaunchKernelGGL((irls_wave_kernel<NT, 2, W, STD, FAM, OFS>), dim3(n_chunks), dim3(64 * W), lds,
                          s, a);
       break;
     default:
-      hipLaunchKernelGGL((irls_wave_kernel<NT, 0, W, STD, FAM>), dim3(n_chunks), dim3(64 * W), lds,
+      hipLaunchKernelGGL((irls_wave_kernel<NT, 0, W, STD, FAM, OFS>), dim3(n_chunks), dim3(64 * W), lds,
                          s, a);
   }
   return hipGetLastError();
 }
 
-template <int NT, bool STD, int FAM>
-static hipError_t launch_wave_sf(const PassArgs& a, int n_chunks, hipStream_t s) {
+template <int NT, bool STD, int FAM, bool OFS = false>
+static hipError_t launch_wave_sf(const typename pass_args_of<OFS>::type& a, int n_chunks,
+                                 hipStream_t s) {
   if constexpr (NT >= 2 && NT <= 7) {
-    if (wave_w(NT, a.waves) == 2) return launch_wave_t<NT, 2, STD, FAM>(a, n_chunks, s);
+    if (wave_w(NT, a.waves) == 2) return launch_wave_t<NT, 2, STD, FAM, OFS>(a, n_chunks, s);
   }
-  return launch_wave_t<NT, 1, STD, FAM>(a, n_chunks, s);
+  return launch_wave_t<NT, 1, STD, FAM, OFS>(a, n_chunks, s);
 }
 
 template <int NT>
@@ -653,13 +673,16 @@ static hipError_t launch_wave_nt(const PassArgs& a, bool std_, int family, int n
               : launch_wave_sf<NT, false, FAMILY_LOGISTIC>(a, n_chunks, s);
 }
 
-// Poisson family (instantiated by the irls_wave_pois_g*.hip units only)
-template <int NT>
-static hipError_t launch_wave_poisson_nt(const PassArgs& a, bool std_, int n_chunks,
-                                         hipStream_t s) {
+// Poisson family (instantiated by the irls_wave_pois_g*.hip units only; OFS,
+// PassArgsOfs with eta_offset set, by the irls_wave_pois_ofs_g*.hip units only)
+template <int NT, bool OFS = false>
+static hipError_t launch_wave_poisson_nt(const typename pass_args_of<OFS>::type& a, bool std_,
+                                         int n_chunks, hipStream_t s) {
   if (!a.slab_llc) return hipErrorInvalidValue;
-  return std_ ? launch_wave_sf<NT, true, FAMILY_POISSON>(a, n_chunks, s)
-              : launch_wave_sf<NT, false, FAMILY_POISSON>(a, n_chunks, s);
+  if constexpr (OFS)
+    if (!a.eta_offset) return hipErrorInvalidValue;
+  return std_ ? launch_wave_sf<NT, true, FAMILY_POISSON, OFS>(a, n_chunks, s)
+              : launch_wave_sf<NT, false, FAMILY_POISSON, OFS>(a, n_chunks, s);
 }
 
 }  // namespace dlsa

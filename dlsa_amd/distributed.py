@@ -110,7 +110,8 @@ def loglik_sharded(X, y, offsets, betas, fit_intercept=False, center=None, scale
 
 
 def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
-                     group=None, codes=None, levels=None, family="logistic", **fit_kw):
+                     group=None, codes=None, levels=None, family="logistic", eta_offset=None,
+                     exposure=None, **fit_kw):
     """Fit this rank's partitions on its GPU and return the global DLSA result.
 
     X, y, offsets describe the LOCAL shard (rows already on this rank's
@@ -120,16 +121,26 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
     partition sums (reference: the shuffle + collect of dlsa/dlsa.py:30-34).
     ``family`` = "logistic" or "poisson" (``poisson_model_batched``: dense
     layout only); everything after the local fits is the same for both.
+    ``eta_offset`` / ``exposure`` (family="poisson" only): the per-row offset
+    of the local shard's rows (``poisson_model_batched_offset``); the combine
+    step never sees it.
     """
     from .models import (logistic_model_batched, logistic_model_batched_categorical,
-                         poisson_model_batched)
+                         poisson_model_batched, poisson_model_batched_offset)
 
     if family not in ("logistic", "poisson"):
         raise ValueError(f"family must be 'logistic' or 'poisson', not {family!r}")
+    if (eta_offset is not None or exposure is not None) and family != "poisson":
+        raise ValueError("eta_offset / exposure need family='poisson'")
     if family == "poisson":
         if codes is not None:
             raise ValueError("family='poisson' runs on the dense layout only (no codes)")
-        fit = poisson_model_batched(X, y, offsets, fit_intercept=fit_intercept, **fit_kw)
+        if eta_offset is not None or exposure is not None:
+            fit = poisson_model_batched_offset(X, y, offsets, eta_offset=eta_offset,
+                                               exposure=exposure, fit_intercept=fit_intercept,
+                                               **fit_kw)
+        else:
+            fit = poisson_model_batched(X, y, offsets, fit_intercept=fit_intercept, **fit_kw)
     elif codes is not None:
         fit = logistic_model_batched_categorical(X, codes, y, offsets, levels,
                                                  fit_intercept=fit_intercept, **fit_kw)

@@ -279,15 +279,51 @@ class BatchedFit:
         return {_hip.STATUS_NAMES.get(int(v), str(v)): int((s == v).sum()) for v in np.unique(s)}
 
 
+def _check_eta_offset(X, eta_offset, exposure):
+    """The argument checks of a per-row offset, before anything touches the
+    GPU: one of ``eta_offset`` / ``exposure`` at most, n entries, and an
+    exposure that is finite and > 0 (its log is the offset)."""
+    if eta_offset is not None and exposure is not None:
+        raise ValueError("give eta_offset or exposure (eta_offset = log exposure), not both")
+    v = eta_offset if eta_offset is not None else exposure
+    if v is None:
+        return
+    n = int(X.shape[0]) if hasattr(X, "shape") else int(np.shape(X)[0])
+    is_t = torch is not None and isinstance(v, torch.Tensor)
+    if (int(v.numel()) if is_t else int(np.size(v))) != n:
+        raise ValueError("eta_offset / exposure must have n entries (one per row of X)")
+    if exposure is not None:
+        if is_t:
+            ok = bool((torch.isfinite(v) & (v > 0)).all())
+        else:
+            a = np.asarray(v, dtype=np.float64)
+            ok = bool(np.isfinite(a).all() and (a > 0).all())
+        if not ok:
+            raise ValueError("exposure must be finite and > 0 (drop the rows with none)")
+
+
+def _dev_eta_offset(eta_offset, exposure, dev):
+    """[n] fp64 offset on the device (log exposure taken there), or None."""
+    if exposure is not None:
+        return torch.log(_dev_f64(exposure, dev).reshape(-1))
+    return _dev_f64(eta_offset, dev).reshape(-1) if eta_offset is not None else None
+
+
 def _glm_model_batched(entry, X, y, offsets, fit_intercept, center, scale, max_iter, tol,
                        hessian, switch_tol, record_timing, rows_per_chunk, workspace, device,
-                       exact, exact_waves, oz_max_bytes):
+                       exact, exact_waves, oz_max_bytes, with_offset=False, eta_offset=None,
+                       exposure=None):
     """The body the iterative families share: checked device copies, outputs,
     options and workspace, then the C-ABI call ``entry`` (an ``*_fit_batched_ex``
-    symbol).  Returns a BatchedFit."""
+    symbol, or with ``with_offset`` one that takes ``eta_offset`` after y: the
+    pointer is null when neither ``eta_offset`` nor ``exposure`` is given).
+    Returns a BatchedFit."""
+    if with_offset:
+        _check_eta_offset(X, eta_offset, exposure)
     dev = _require_gpu(device)
     Xd = _dev_f64(X, dev)
     yd = _dev_f64(y, dev).reshape(-1)
+    od = _dev_eta_offset(eta_offset, exposure, dev) if with_offset else None
     if Xd.dim() != 2:
         raise ValueError("X must be 2-D [n, p]")
     n, p = Xd.shape
@@ -333,7 +369,8 @@ def _glm_model_batched(entry, X, y, offsets, fit_intercept, center, scale, max_i
     opt.workspace = workspace.data_ptr()
     opt.workspace_bytes = workspace.numel()
     rc = getattr(lib, entry)(
-        _ptr(Xd), _ptr(yd), offs_p, K, p, int(bool(fit_intercept)), _ptr(cd), _ptr(sd),
+        _ptr(Xd), _ptr(yd), *([_ptr(od)] if with_offset else []), offs_p, K, p,
+        int(bool(fit_intercept)), _ptr(cd), _ptr(sd),
         int(max_iter), float(tol), _ptr(theta), _ptr(sig), _ptr(sigt), _ptr(ll), _ptr(iters),
         _ptr(status), ctypes.byref(opt), _stream(dev))
     _hip.check(rc, entry)
@@ -392,6 +429,29 @@ def poisson_model_batched(X, y, offsets, fit_intercept=False, center=None, scale
     return _glm_model_batched("dlsa_poisson_fit_batched_ex", X, y, offsets, fit_intercept, center,
                               scale, max_iter, tol, hessian, switch_tol, record_timing,
                               rows_per_chunk, workspace, device, "auto", exact_waves, 0)
+
+
+def poisson_model_batched_offset(X, y, offsets, eta_offset=None, exposure=None,
+                                 fit_intercept=False, center=None, scale=None, max_iter=100,
+                                 tol=1e-10, hessian="mixed", switch_tol=1e-6,
+                                 record_timing=False, rows_per_chunk=0, workspace=None,
+                                 device=None, exact_waves=0):
+    """``poisson_model_batched`` for rate data: ``eta = x . theta + eta_offset``
+    with a known per-row ``eta_offset`` [n] (R's ``glm(offset=)``), or
+    ``exposure`` [n] > 0 whose log, taken on the device, is the offset
+    (statsmodels' ``exposure=``); both raise ``ValueError``, as does a wrong
+    length or an exposure that is not finite and positive.  (``offsets`` stays
+    the partition boundaries.)  Neither given: exactly ``poisson_model_batched``.
+    Sig_inv and the log-likelihood are taken at mu = exp(eta) with the offset.
+    With an intercept the fit starts at log(sum y / sum exp(eta_offset)); a
+    partition with a non-finite ``eta_offset`` gets status "nonfinite" and
+    all-zero outputs, the others are unaffected
+    (``dlsa_poisson_fit_batched_offset``).  The other arguments, the limit
+    P <= 192 and the result as ``poisson_model_batched``."""
+    return _glm_model_batched("dlsa_poisson_fit_batched_offset", X, y, offsets, fit_intercept,
+                              center, scale, max_iter, tol, hessian, switch_tol, record_timing,
+                              rows_per_chunk, workspace, device, "auto", exact_waves, 0,
+                              with_offset=True, eta_offset=eta_offset, exposure=exposure)
 
 
 def _cat_inputs(Xn, codes, y, offsets, levels, center, scale, dev):
@@ -539,12 +599,17 @@ def _loglik_groups(call, betas, P, K, dev, return_sum):
     return (out, total) if return_sum else out
 
 
-def _loglik_dense(entry, X, y, offsets, betas, fit_intercept, center, scale, device, return_sum):
+def _loglik_dense(entry, X, y, offsets, betas, fit_intercept, center, scale, device, return_sum,
+                  with_offset=False, eta_offset=None, exposure=None):
     """The dense evaluation pass of one family (``entry``: a
-    ``*_loglik_batched_sum`` symbol) through ``_loglik_groups``."""
+    ``*_loglik_batched_sum`` symbol, or with ``with_offset`` one that takes
+    ``eta_offset`` after y) through ``_loglik_groups``."""
+    if with_offset:
+        _check_eta_offset(X, eta_offset, exposure)
     dev = _require_gpu(device)
     Xd = _dev_f64(X, dev)
     yd = _dev_f64(y, dev).reshape(-1)
+    od = _dev_eta_offset(eta_offset, exposure, dev) if with_offset else None
     n, p = Xd.shape
     offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
     K = offs.size - 1
@@ -557,8 +622,8 @@ def _loglik_dense(entry, X, y, offsets, betas, fit_intercept, center, scale, dev
     fn = getattr(_hip.load(), entry)
 
     def call(bd, g, out, total):
-        rc = fn(_ptr(Xd), _ptr(yd), offs.ctypes.data_as(ctypes.c_void_p), K, p,
-                int(bool(fit_intercept)), _ptr(cd), _ptr(sd), _ptr(bd), g, _ptr(out), _ptr(total),
+        rc = fn(_ptr(Xd), _ptr(yd), *([_ptr(od)] if with_offset else []),
+                offs.ctypes.data_as(ctypes.c_void_p), K, p, int(bool(fit_intercept)), _ptr(cd), _ptr(sd), _ptr(bd), g, _ptr(out), _ptr(total),
                 _stream(dev))
         _hip.check(rc, entry)
 
@@ -585,6 +650,19 @@ def poisson_loglik_batched(X, y, offsets, betas, fit_intercept=False, center=Non
     limits (P <= 512, 16 candidates to a pass) and outputs."""
     return _loglik_dense("dlsa_poisson_loglik_batched_sum", X, y, offsets, betas, fit_intercept,
                          center, scale, device, return_sum)
+
+
+def poisson_loglik_batched_offset(X, y, offsets, betas, eta_offset=None, exposure=None,
+                                  fit_intercept=False, center=None, scale=None, device=None,
+                                  return_sum=False):
+    """``poisson_loglik_batched`` with the per-row offset of
+    ``poisson_model_batched_offset``: eta = x . beta + eta_offset for every
+    candidate (``eta_offset`` [n], or ``exposure`` [n] > 0 whose log is taken on
+    the device; the same ``ValueError`` cases).  Neither given: exactly
+    ``poisson_loglik_batched``."""
+    return _loglik_dense("dlsa_poisson_loglik_batched_sum_offset", X, y, offsets, betas,
+                         fit_intercept, center, scale, device, return_sum, with_offset=True,
+                         eta_offset=eta_offset, exposure=exposure)
 
 
 def logistic_loglik_batched_categorical(Xn, codes, y, offsets, levels, betas, fit_intercept=False,

@@ -257,6 +257,36 @@ int dlsa_poisson_fit_batched_ex(const double* X, const double* y,
                                 const dlsa_fit_options* opt, void* stream);
 
 /*
+ * dlsa_poisson_fit_batched_ex with a per-row offset of the linear predictor
+ * (rate models: eta_offset = log exposure, R's glm(offset=)):
+ *   eta_i = x_i . theta + eta_offset_i,  mu_i = exp(eta_i).
+ *  eta_offset  [n_total] fp64, device, finite; row i belongs to row i of X.
+ *              NULL: exactly dlsa_poisson_fit_batched_ex (the same kernels,
+ *              bit-identical outputs).
+ * (`offsets` stays the partition boundaries; the two are unrelated.)
+ * All other arguments and the outputs as there; sig_inv = X^T diag(mu) X and
+ * loglik are taken at the mu above.  The offset is one more 8 B/row stream of
+ * the passes; nothing per row is stored and the workspace is unchanged.
+ * Start point: with an intercept theta = (log(sum y_k / sum exp(eta_offset_k)),
+ * 0, ..., 0), the MLE of the intercept-only rate model; without one theta = 0.
+ * Restarts go back to it.  Beside the rules of dlsa_poisson_fit_batched_ex, a
+ * partition with a non-finite eta_offset, or whose sum exp(eta_offset) is not
+ * finite and positive, ends DLSA_STATUS_NONFINITE before any pass with
+ * all-zero outputs; the other partitions are not affected.  A zero exposure
+ * (eta_offset = -inf) is the caller's row to drop.
+ * Limit: P <= DLSA_MAX_P_FUSED (192), else DLSA_E_UNSUPPORTED before any launch.
+ */
+int dlsa_poisson_fit_batched_offset(const double* X, const double* y,
+                                    const double* eta_offset,
+                                    const int64_t* offsets, int32_t K, int32_t p,
+                                    int32_t fit_intercept, const double* center,
+                                    const double* scale, int32_t max_iter,
+                                    double tol, double* theta, double* sig_inv,
+                                    double* sig_inv_theta, double* loglik,
+                                    int32_t* iters, int32_t* status,
+                                    const dlsa_fit_options* opt, void* stream);
+
+/*
  * dlsa_logistic_loglik_batched_sum for the Poisson family:
  *   loglik[k * n_beta + b] = sum_i y_i eta_i - exp(eta_i) - lgamma(y_i + 1),
  * eta_i = x_i . beta_b.  Same arguments, limits (P <= 512, 1 <= n_beta <= 16)
@@ -268,6 +298,21 @@ int dlsa_poisson_loglik_batched_sum(const double* X, const double* y,
                                     const double* scale, const double* betas,
                                     int32_t n_beta, double* loglik, double* loglik_sum,
                                     void* stream);
+
+/*
+ * dlsa_poisson_loglik_batched_sum with the per-row offset of
+ * dlsa_poisson_fit_batched_offset: eta_i = x_i . beta_b + eta_offset_i for every
+ * candidate (the constant lgamma(y + 1) is unchanged).  eta_offset [n_total]
+ * fp64, device; NULL: exactly dlsa_poisson_loglik_batched_sum.
+ */
+int dlsa_poisson_loglik_batched_sum_offset(const double* X, const double* y,
+                                           const double* eta_offset,
+                                           const int64_t* offsets, int32_t K,
+                                           int32_t p, int32_t fit_intercept,
+                                           const double* center, const double* scale,
+                                           const double* betas, int32_t n_beta,
+                                           double* loglik, double* loglik_sum,
+                                           void* stream);
 
 /*
  * Batched local OLS fit (the linear DLSA path; the
