@@ -43,11 +43,12 @@ static int fit_dense(int family, const double* X, const double* y, const int64_t
     return DLSA_E_INVALID;
   }
   const int P = p + (fit_intercept ? 1 : 0);
+  const FamilyRules rules = family_rules(family);
   if (P > DLSA_MAX_P) {
     set_error("P = p + intercept > " + std::to_string(DLSA_MAX_P) + " is not supported");
     return DLSA_E_UNSUPPORTED;
   }
-  if (family == FAMILY_POISSON && P > DLSA_MAX_P_FUSED) {
+  if (P > rules.max_p) {  // (the Poisson family: fused path only)
     set_error("Poisson fit: P = p + intercept > DLSA_MAX_P_FUSED = " +
               std::to_string(DLSA_MAX_P_FUSED) + " is not supported");
     return DLSA_E_UNSUPPORTED;
@@ -58,7 +59,7 @@ static int fit_dense(int family, const double* X, const double* y, const int64_t
     set_error("null X or y");
     return DLSA_E_INVALID;
   }
-  if (family == FAMILY_GAUSSIAN) f.max_iter = 1;  // closed form: one exact fp64 pass
+  if (!rules.iterates) f.max_iter = 1;  // closed form: one exact fp64 pass
   return P > DLSA_MAX_P_FUSED ? fit_wide(f) : fit_fused(f);
 }
 
@@ -196,8 +197,10 @@ int dlsa_logistic_fit_batched(const double* X, const double* y, const int64_t* o
                                       iters, status, nullptr, stream);
 }
 
-static int loglik_dense(int family, const double* X, const double* y, const int64_t* offsets, int32_t K,
-                        int32_t p, int32_t fit_intercept, const double* center,
+// (entry: the name the argument check reports)
+static int loglik_dense(int family, const char* entry, const double* X, const double* y,
+                        const int64_t* offsets, int32_t K, int32_t p, int32_t fit_intercept,
+                        const double* center,
                         const double* scale, const double* betas, int32_t n_beta,
                         double* loglik, double* loglik_sum, void* stream_,
                         const double* eta_offset = nullptr) {
@@ -208,9 +211,7 @@ static int loglik_dense(int family, const double* X, const double* y, const int6
   const int P = p + (fit_intercept ? 1 : 0);
   if (p < 0 || P < 1 || P > 512 || n_beta < 1 || n_beta > 16 || !betas || !loglik ||
       (center == nullptr) != (scale == nullptr)) {
-    set_error(std::string(family == FAMILY_POISSON ? "dlsa_poisson_loglik_batched_sum"
-                                                   : "dlsa_logistic_loglik_batched") +
-              ": invalid arguments (1 <= P <= 512, 1 <= n_beta <= 16)");
+    set_error(std::string(entry) + ": invalid arguments (1 <= P <= 512, 1 <= n_beta <= 16)");
     return DLSA_E_INVALID;
   }
   const int64_t n_total = offsets[K];
@@ -271,7 +272,8 @@ int dlsa_logistic_loglik_batched(const double* X, const double* y, const int64_t
                                  const double* center, const double* scale,
                                  const double* betas, int32_t n_beta, double* loglik,
                                  void* stream) {
-  return loglik_dense(FAMILY_LOGISTIC, X, y, offsets, K, p, fit_intercept, center, scale, betas,
+  return loglik_dense(FAMILY_LOGISTIC, "dlsa_logistic_loglik_batched", X, y, offsets, K, p,
+                      fit_intercept, center, scale, betas,
                       n_beta, loglik, nullptr, stream);
 }
 
@@ -280,7 +282,8 @@ int dlsa_logistic_loglik_batched_sum(const double* X, const double* y, const int
                                      const double* center, const double* scale,
                                      const double* betas, int32_t n_beta, double* loglik,
                                      double* loglik_sum, void* stream) {
-  return loglik_dense(FAMILY_LOGISTIC, X, y, offsets, K, p, fit_intercept, center, scale, betas,
+  return loglik_dense(FAMILY_LOGISTIC, "dlsa_logistic_loglik_batched", X, y, offsets, K, p,
+                      fit_intercept, center, scale, betas,
                       n_beta, loglik, loglik_sum, stream);
 }
 
@@ -289,7 +292,8 @@ int dlsa_poisson_loglik_batched_sum(const double* X, const double* y, const int6
                                     const double* center, const double* scale,
                                     const double* betas, int32_t n_beta, double* loglik,
                                     double* loglik_sum, void* stream) {
-  return loglik_dense(FAMILY_POISSON, X, y, offsets, K, p, fit_intercept, center, scale, betas,
+  return loglik_dense(FAMILY_POISSON, "dlsa_poisson_loglik_batched_sum", X, y, offsets, K, p,
+                      fit_intercept, center, scale, betas,
                       n_beta, loglik, loglik_sum, stream);
 }
 
@@ -299,7 +303,8 @@ int dlsa_poisson_loglik_batched_sum_offset(const double* X, const double* y,
                                            const double* center, const double* scale,
                                            const double* betas, int32_t n_beta, double* loglik,
                                            double* loglik_sum, void* stream) {
-  return loglik_dense(FAMILY_POISSON, X, y, offsets, K, p, fit_intercept, center, scale, betas,
+  return loglik_dense(FAMILY_POISSON, "dlsa_poisson_loglik_batched_sum", X, y, offsets, K, p,
+                      fit_intercept, center, scale, betas,
                       n_beta, loglik, loglik_sum, stream, eta_offset);
 }
 

@@ -5,6 +5,8 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
+#include <utility>
 
 #include "../../include/dlsa_hip.h"
 
@@ -33,6 +35,70 @@ constexpr int kRunPhases = 3;
 enum : int32_t { STATUS_RUNNING = -1 };
 // FAMILY_POISSON (log link): iterative like the logistic family; fused path only
 enum : int32_t { FAMILY_LOGISTIC = 0, FAMILY_GAUSSIAN = 1, FAMILY_POISSON = 2 };
+
+// What a family may launch: the one place the fits (capi.hip, fit_fused.hip,
+// fit_wide.hip) and the pass launchers read it from, at run time or in
+// `if constexpr`.
+struct FamilyRules {
+  // Newton to tol at the fit's Hessian mode; else one exact pass: PREC_F64
+  // only, max_iter = 1, no warm-start levels, no polish
+  bool iterates;
+  // may record the digit scales (colmax / zcolmax) and take the int8 exact pass
+  bool digit_scales;
+  // fp64 passes sum the log-likelihood's constant term into slab_llc
+  bool sums_ll_const;
+  // starts from a device-computed point (launch_poisson_start), which may end partitions
+  bool device_start;
+  // may carry a per-row eta_offset (the OFS kernels, PassArgsOfs)
+  bool offset;
+  int max_p;  // largest P = p + intercept
+};
+constexpr FamilyRules kLogisticRules = {true, true, false, false, false, DLSA_MAX_P};
+constexpr FamilyRules kGaussianRules = {false, false, false, false, false, DLSA_MAX_P};
+constexpr FamilyRules kPoissonRules = {true, false, true, true, true, DLSA_MAX_P_FUSED};
+constexpr FamilyRules family_rules(int family) {
+  return family == FAMILY_GAUSSIAN ? kGaussianRules
+         : family == FAMILY_POISSON ? kPoissonRules
+                                    : kLogisticRules;
+}
+
+// A compilation unit of a pass (irls_coop*.hip, irls_wave*.hip, irls_oz*.hip)
+// instantiates the launchers of one set of families and one list of NT.
+template <int... V>
+struct IntList {
+  static constexpr unsigned mask = ((1u << V) | ...);
+};
+typedef IntList<FAMILY_LOGISTIC> FamLogistic;
+typedef IntList<FAMILY_LOGISTIC, FAMILY_GAUSSIAN> FamLogisticGaussian;
+typedef IntList<FAMILY_POISSON> FamPoisson;
+// f(integral_constant FAM, integral_constant NT) of the run-time (family, NT);
+// hipErrorInvalidValue for a pair the unit does not hold
+template <int... FAMS, int... NTS, typename F>
+inline hipError_t unit_dispatch(IntList<FAMS...>, IntList<NTS...>, int family, int NT, F&& f) {
+  hipError_t e = hipErrorInvalidValue;
+  auto by_nt = [&](auto fam) {
+    (void)((NT == NTS && ((e = f(fam, std::integral_constant<int, NTS>{})), true)) || ...);
+  };
+  (void)((family == FAMS && (by_nt(std::integral_constant<int, FAMS>{}), true)) || ...);
+  return e;
+}
+// Row of a pass's routing table: the unit entry point that holds the
+// instantiations of these families, with / without the offset, for NT in
+// [nt_lo, nt_hi]
+template <typename Fn>
+struct UnitRow {
+  unsigned families;  // IntList::mask
+  bool ofs;
+  int nt_lo, nt_hi;
+  Fn* launch;
+};
+template <typename Fn, size_t N>
+inline Fn* find_unit(const UnitRow<Fn> (&table)[N], int family, bool ofs, int NT) {
+  for (const UnitRow<Fn>& r : table)
+    if (((r.families >> family) & 1u) && r.ofs == ofs && NT >= r.nt_lo && NT <= r.nt_hi)
+      return r.launch;
+  return nullptr;
+}
 
 // Cache policy of the LDS-DMA loads that stream X (the aux / cpol operand of
 // buffer_load ... lds; profiling builds override it, tools/build_variants.sh).
@@ -154,6 +220,47 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(uintptr_t base, u
   return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), (short)0, (int)nr,
                                            0x00020000);
 }
+
+typedef __attribute__((address_space(3))) void lds_void_t;
+typedef const __attribute__((address_space(1))) void gbl_void_t;
+
+// s_waitcnt vmcnt(N); wait_vmcnt_le<N>(n): vmcnt(min(n, N)) for a run-time n
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits on gfx950");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void wait_vmcnt_le(int n) {
+  if constexpr (N <= 0) {
+    wait_vmcnt<0>();
+  } else {
+    if (n >= N)
+      wait_vmcnt<N>();
+    else
+      wait_vmcnt_le<N - 1>(n);
+  }
+}
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>)
+template <typename F, int... Is>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
+  (f(std::integral_constant<int, Is>{}), ...);
+}
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// chunk_row0[chunk] with both dwords wave-uniform (SGPRs)
+__device__ __forceinline__ int64_t uniform_row0(const int64_t* chunk_row0, int chunk) {
+  return ((int64_t)__builtin_amdgcn_readfirstlane((int)(chunk_row0[chunk] >> 32)) << 32) |
+         (uint32_t)__builtin_amdgcn_readfirstlane((int)chunk_row0[chunk]);
+}
+
+// (The ring zeroing and the center / 1/scale fill of the pass kernels are not
+// helpers: as inlined functions they changed the register allocation of the
+// standardising cooperative and per-wave kernels, tools/kernel_diff.py.)
 
 // v of the lane that DPP control CTRL selects, both dwords
 template <int CTRL>

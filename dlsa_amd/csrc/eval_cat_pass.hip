@@ -19,26 +19,7 @@ namespace dlsa {
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void gbl_void_t;
-
 constexpr int CW = 4;  // waves
-
-template <int N>
-__device__ __forceinline__ void ec_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void ec_wait_le(int n) {
-  if constexpr (N <= 0) {
-    ec_wait<0>();
-  } else {
-    if (n >= N)
-      ec_wait<N>();
-    else
-      ec_wait_le<N - 1>(n);
-  }
-}
 
 // 1 KiB pieces (64 lanes x 16 B) that cover `bytes` from any start inside a
 // 16-byte granule
@@ -168,7 +149,7 @@ __global__ __launch_bounds__(256) void loglik_cat_kernel(const EvalCatArgs a) {
   for (int b = 0; b < nslot - 1; ++b) issue(b);
   const int keep = (nslot - 2) * per_blk;
   for (int blk = 0; blk < nb; ++blk) {
-    ec_wait_le<40>(keep);
+    wait_vmcnt_le<40>(keep);
     __syncthreads();
     issue(blk + nslot - 1);
     const char* slot = smem + (blk % nslot) * g.slot_bytes;
@@ -222,7 +203,7 @@ __global__ __launch_bounds__(256) void loglik_cat_kernel(const EvalCatArgs a) {
       }
     }
   }
-  ec_wait<0>();
+  wait_vmcnt<0>();
   __syncthreads();
 #pragma unroll
   for (int b = 0; b < BP; ++b) {

@@ -14,38 +14,14 @@ namespace dlsa {
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void gbl_void_t;
-
 constexpr int EW = 4;    // waves
 constexpr int ERB = 32;  // rows per block
 constexpr int EMAXB = 16;
 
-template <int N>
-__device__ __forceinline__ void ev_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void ev_wait_le(int n) {
-  if constexpr (N <= 0) {
-    ev_wait<0>();
-  } else {
-    if (n >= N)
-      ev_wait<N>();
-    else
-      ev_wait_le<N - 1>(n);
-  }
-}
-template <int CTRL>
-__device__ __forceinline__ double ev_dpp(double v) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ double ev_red8(double v) {
-  v += ev_dpp<0xB1>(v);
-  v += ev_dpp<0x4E>(v);
-  v += ev_dpp<0x141>(v);
+  v += dpp_f64<0xB1>(v);
+  v += dpp_f64<0x4E>(v);
+  v += dpp_f64<0x141>(v);
   return v;
 }
 __host__ __device__ __forceinline__ int ev_npieces(int p) {
@@ -135,7 +111,7 @@ __global__ __launch_bounds__(256) void loglik_eval_kernel(const EvalArgs a) {
   // 4 KiB piece rows) and nslot <= 6, so keep <= 4 (6 + 2) = 32 <= the bound
   const int keep = (nslot - 2) * (d + NLD);
   for (int blk = 0; blk < nb; ++blk) {
-    ev_wait_le<40>(keep);
+    wait_vmcnt_le<40>(keep);
     __syncthreads();
     issue(blk + nslot - 1);
     const char* slot = smem + (blk % nslot) * slot_bytes;
@@ -174,7 +150,7 @@ __global__ __launch_bounds__(256) void loglik_eval_kernel(const EvalArgs a) {
       }
     }
   }
-  ev_wait<0>();
+  wait_vmcnt<0>();
   __syncthreads();
 #pragma unroll
   for (int b = 0; b < EMAXB; ++b) {
@@ -198,10 +174,12 @@ hipError_t launch_loglik_eval(const EvalArgs& a, int family, int n_chunks, hipSt
   const int PM = ((a.P + 7) / 8) * 8;
   const size_t lds = (size_t)a.nslot * a.slot_bytes +
                      ((size_t)a.nbeta * PM + 2 * PM + EW * EMAXB) * sizeof(double);
-  if (a.eta_offset && family != FAMILY_POISSON) return hipErrorInvalidValue;
-  auto kern = family != FAMILY_POISSON ? loglik_eval_kernel<FAMILY_LOGISTIC>
-              : a.eta_offset           ? loglik_eval_kernel<FAMILY_POISSON, true>
-                                       : loglik_eval_kernel<FAMILY_POISSON>;
+  const FamilyRules rules = family_rules(family);
+  if (a.eta_offset && !rules.offset) return hipErrorInvalidValue;
+  // the family whose log-likelihood has a constant term has its own kernel
+  auto kern = !rules.sums_ll_const ? loglik_eval_kernel<FAMILY_LOGISTIC>
+              : a.eta_offset       ? loglik_eval_kernel<FAMILY_POISSON, true>
+                                   : loglik_eval_kernel<FAMILY_POISSON>;
   {
     hipError_t e = ensure_max_lds((const void*)kern, 160 * 1024);
     if (e != hipSuccess) return e;

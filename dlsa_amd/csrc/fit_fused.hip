@@ -108,6 +108,7 @@ void FusedFit::set_pass_args(const Plan& pl, const Workspace& ws, const Layout& 
 hipError_t FusedFit::pass(int ph, const Plan& q, bool full, const std::vector<int64_t>& part_rows,
                           const int32_t* hph) {
   const int family = f.family;
+  const FamilyRules rules = family_rules(family);
   const bool f64 = ph == PHASE_F64;
   const int prec = f64 ? PREC_F64 : (ph == PHASE_F32X ? PREC_F32 : approx_prec);
   pa.want_phase = ph;
@@ -151,7 +152,7 @@ hipError_t FusedFit::pass(int ph, const Plan& q, bool full, const std::vector<in
     // OLS (one pass at theta = 0): X streamed into registers, no LDS ring.
     // Its buffer range and row offsets are 32-bit: a caller's rows_per_chunk
     // of >= 2^31 bytes per chunk takes the per-wave kernel instead
-    if (f64 && family == FAMILY_GAUSSIAN && ols_stream_applies(q.NT) &&
+    if (f64 && !rules.iterates && ols_stream_applies(q.NT) &&
         (int64_t)q.max_chunk_rows * f.p * 8 < (1LL << 31))
       return launch_ols_stream(pc, q.NT, standardize, q.n_chunks, stream);
     if (wave) return launch_irls_wave(pc, q.NT, standardize, family, q.n_chunks, stream);
@@ -215,10 +216,11 @@ void FusedFit::count_spec_pass(bool final_level, const std::vector<int64_t>& par
 int FusedFit::run() {
   const dlsa_fit_options& opt = f.start.opt;
   const int family = f.family;
+  const FamilyRules rules = family_rules(family);
   const int64_t* offsets = f.offsets;
   // warm-start levels: Newton on row prefixes (1/16) before all rows
   const std::vector<Plan> plans =
-      level_plans(offsets, K, f.p, f.fit_intercept, family != FAMILY_GAUSSIAN && opt.warm_start,
+      level_plans(offsets, K, f.p, f.fit_intercept, rules.iterates && opt.warm_start,
                   [&](double, int64_t) { return opt.rows_per_chunk; });
   const Plan& pl = plans.back();
   const Layout L = make_layout(pl, K);
@@ -254,7 +256,7 @@ int FusedFit::run() {
   // Poisson: the K start values and the per-chunk constant-term partials live
   // in an allocation of the fit's own (the workspace layout is the logistic one)
   Workspace pws(stream);
-  if (family == FAMILY_POISSON) {
+  if (rules.device_start || rules.sums_ll_const) {
     Bump pb;
     const int64_t off_t0 = pb.take(8LL * std::max(K, 1));
     const int64_t off_llc = pb.take(8LL * std::max(pl.n_chunks, 1));
@@ -266,9 +268,9 @@ int FusedFit::run() {
   set_pass_args(pl, ws, L);
 
   const int start_phase =
-      (opt.hessian_mode == DLSA_HESSIAN_FP64 || family == FAMILY_GAUSSIAN) ? PHASE_F64 : PHASE_F32;
+      (opt.hessian_mode == DLSA_HESSIAN_FP64 || !rules.iterates) ? PHASE_F64 : PHASE_F32;
   DLSA_HIP_TRY(fit_init(sa, d_offsets, K, start_phase, stream));
-  if (family == FAMILY_POISSON)  // the start point; ends the partitions that have no MLE
+  if (rules.device_start)  // Poisson: the start point; ends the partitions that have no MLE
     DLSA_HIP_TRY(launch_poisson_start(f.y, d_offsets, K, P, f.fit_intercept ? 1 : 0, sa.theta,
                                       const_cast<double*>(sa.theta0), sa.phase, sa.status, stream,
                                       f.eta_offset));
@@ -281,7 +283,7 @@ int FusedFit::run() {
   const bool trace = trace_enabled();
 
   // (Poisson weights are unbounded: no int8 exact pass, DLSA_EXACT_AUTO is fp64 MFMA)
-  use_oz = family != FAMILY_POISSON && opt.exact_pass != DLSA_EXACT_FP64 &&
+  use_oz = rules.digit_scales && opt.exact_pass != DLSA_EXACT_FP64 &&
            approx_prec == PREC_BF16 && oz_applies(pl.NT, f.p) && pl.max_chunk_rows <= kOzMaxRows;
   d_colmax = (uint32_t*)ws.at(L.off_colmax);
   d_zcolmax = (uint32_t*)ws.at(L.off_zcolmax);
@@ -305,7 +307,7 @@ int FusedFit::run() {
       DLSA_HIP_TRY(reenter_level(sa, K, start_phase, h, n_running, stream));
     else
       DLSA_HIP_TRY(read_phases(sa, K, h, stream));
-    if (lvl == 0 && family == FAMILY_POISSON) {  // less the partitions the start point ended
+    if (lvl == 0 && rules.device_start) {  // less the partitions the start point ended
       n_running[start_phase] = 0;
       for (int k = 0; k < K; ++k)
         if (h.phase[k] == start_phase) n_running[start_phase]++;
@@ -349,7 +351,7 @@ int FusedFit::run() {
   // polish: partitions the budget left running (any phase) get one exact pass
   // at the theta they return; its X^T W X is published as Sig_inv, no step
   // (models.py:114,130 evaluate the weights at the coef sklearn stopped at)
-  if (family != FAMILY_GAUSSIAN && running_total(n_running) > 0 && pl.n_chunks > 0) {
+  if (rules.iterates && running_total(n_running) > 0 && pl.n_chunks > 0) {
     // (the final level's plan, pl, is on the device: it was the last uploaded)
     // a partition stopped in an approximate phase took a full step after its
     // last record: its polish pass cannot use that record

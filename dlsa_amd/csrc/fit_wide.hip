@@ -11,12 +11,13 @@ int fit_wide(const DenseFit& f) {
   const dlsa_fit_options& opt = f.start.opt;
   hipStream_t stream = f.start.stream;
   const int family = f.family, K = f.K, p = f.p;
+  const FamilyRules rules = family_rules(family);
   const int64_t* offsets = f.offsets;
   const int P = p + (f.fit_intercept ? 1 : 0);
   const int NB = (P + kWideTile - 1) / kWideTile;
   const std::vector<WidePlans> plans = wide_level_plans(
       offsets, K, p, f.fit_intercept, opt.rows_per_chunk,
-      family == FAMILY_LOGISTIC && opt.warm_start);
+      rules.iterates && opt.warm_start);
   const WideLayout L = make_wide_layout(plans, K, offsets[K], P);
   g_stats.n_chunks = plans.back().gram.n_chunks;
 
@@ -27,7 +28,7 @@ int fit_wide(const DenseFit& f) {
   // caller workspace of at least base_total but less than total bytes, a
   // failed allocation, or opt.oz_max_bytes below the records' size -- the
   // fp64 Gram runs (stats.oz_fallbacks).  DLSA_EXACT_FP64: always the fp64 Gram.
-  bool use_wide_oz = opt.exact_pass != DLSA_EXACT_FP64 && family == FAMILY_LOGISTIC &&
+  bool use_wide_oz = opt.exact_pass != DLSA_EXACT_FP64 && rules.digit_scales &&
                      opt.hessian_mode == DLSA_HESSIAN_MIXED && L.digit_bytes > 0;
   if (use_wide_oz && opt.oz_max_bytes > 0 && L.digit_bytes > opt.oz_max_bytes) {
     use_wide_oz = false;
@@ -87,7 +88,7 @@ int fit_wide(const DenseFit& f) {
   // MIXED / MIXED_F32: bf16-MFMA Gram passes until the step is below
   // switch_tol, then fp64 Gram passes (the fused path's phase machine)
   const int start_phase =
-      (opt.hessian_mode == DLSA_HESSIAN_FP64 || family == FAMILY_GAUSSIAN) ? PHASE_F64 : PHASE_F32;
+      (opt.hessian_mode == DLSA_HESSIAN_FP64 || !rules.iterates) ? PHASE_F64 : PHASE_F32;
   DLSA_HIP_TRY(fit_init(sa, d_offsets, K, start_phase, stream));
   int n_running[kRunPhases] = {0, 0, 0};
   for (int k = 0; k < K; ++k)
@@ -187,7 +188,7 @@ int fit_wide(const DenseFit& f) {
   g_stats.iterations = it;
   // polish: partitions the budget left running get Sig_inv = X^T W X at the
   // theta they return (row pass + exact Gram pass, no step)
-  if (family == FAMILY_LOGISTIC && running_total(n_running) > 0 && plans.back().rows.n_chunks > 0) {
+  if (rules.iterates && running_total(n_running) > 0 && plans.back().rows.n_chunks > 0) {
     const WidePlans& q = plans.back();
     DLSA_HIP_TRY(mark_polish(sa, K, h, stream));
     DLSA_HIP_TRY(exact_gram(q, true));

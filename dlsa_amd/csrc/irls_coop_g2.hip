@@ -3,13 +3,6 @@
 
 namespace dlsa {
 
-hipError_t launch_irls_coop_g2(const PassArgs& a, int NT, int prec, bool std_, int family,
-                                int n_chunks, hipStream_t s) {
-  switch (NT) {
-    case 5: return launch_coop_nt<5>(a, prec, std_, family, n_chunks, s);
-    case 6: return launch_coop_nt<6>(a, prec, std_, family, n_chunks, s);
-    default: return hipErrorInvalidValue;
-  }
-}
+DLSA_COOP_UNIT(launch_irls_coop_g2, FamLogisticGaussian, false, 5, 6)
 
 }  // namespace dlsa

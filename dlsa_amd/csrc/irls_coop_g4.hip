@@ -3,12 +3,6 @@
 
 namespace dlsa {
 
-hipError_t launch_irls_coop_g4(const PassArgs& a, int NT, int prec, bool std_, int family,
-                                int n_chunks, hipStream_t s) {
-  switch (NT) {
-    case 8: return launch_coop_nt<8>(a, prec, std_, family, n_chunks, s);
-    default: return hipErrorInvalidValue;
-  }
-}
+DLSA_COOP_UNIT(launch_irls_coop_g4, FamLogisticGaussian, false, 8)
 
 }  // namespace dlsa

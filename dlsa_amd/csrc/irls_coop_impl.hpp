@@ -40,8 +40,6 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2c __attribute__((ext_vector_type(2)));
 typedef float f2c __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void gbl_void_t;
 
 namespace {
 
@@ -57,23 +55,6 @@ constexpr int RB = kCoopRows;   // rows per block
 // semi-definite by construction, as in the wide fused pass), instead of the
 // two images x and w x -- half the image stores and LDS: 9.87 -> 9.37 ms per
 // config-2 launch (profiles/r02ac_zimage_ab.txt)
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits on gfx950");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt_le(int n) {
-  if constexpr (N <= 0) {
-    wait_vmcnt<0>();
-  } else {
-    if (n >= N)
-      wait_vmcnt<N>();
-    else
-      wait_vmcnt_le<N - 1>(n);
-  }
-}
 
 // Lane l and lane l ^ 16 (permlane16_swap), l and l ^ 32 (permlane32_swap):
 // both operands are v, so the swapped pair (x, y) holds the two halves and
@@ -141,15 +122,6 @@ struct CG {
     return m;
   }
 };
-
-template <typename F, int... Is>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 __host__ __device__ __forceinline__ int npieces_for(int p) { return (RB * p * 8 + 16 + 1023) / 1024; }
 
@@ -269,9 +241,7 @@ void irls_coop_kernel(const typename pass_args_of<OFS>::type a) {
   const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int p = a.p, P = a.P, ic = a.intercept;
-  const int64_t row0 =
-      ((int64_t)__builtin_amdgcn_readfirstlane((int)(a.chunk_row0[chunk] >> 32)) << 32) |
-      (uint32_t)__builtin_amdgcn_readfirstlane((int)a.chunk_row0[chunk]);
+  const int64_t row0 = uniform_row0(a.chunk_row0, chunk);
   const int nrows = __builtin_amdgcn_readfirstlane(a.chunk_rows[chunk]);
   const int nb = (nrows + RB - 1) / RB;
   const int nslot = a.nslot;
@@ -608,68 +578,59 @@ static hipError_t launch_c(const typename pass_args_of<OFS>::type& a, int n_chun
   return hipGetLastError();
 }
 
-template <int NT, int W>
-static hipError_t launch_coop_ntw(const PassArgs& a, int prec, bool std_, int family,
-                                  int n_chunks, hipStream_t s) {
-  if (family == FAMILY_GAUSSIAN) {
-    if (prec != PREC_F64) return hipErrorInvalidValue;
-    return std_ ? launch_c<NT, W, PREC_F64, true, FAMILY_GAUSSIAN>(a, n_chunks, s)
-                : launch_c<NT, W, PREC_F64, false, FAMILY_GAUSSIAN>(a, n_chunks, s);
-  }
-  if (family == FAMILY_POISSON) return hipErrorInvalidValue;  // launch_coop_poisson_nt
-  switch (prec) {
-    case PREC_BF16:
-      if constexpr (NT <= kOzMaxNT) {
-        const int cm = (a.colmax ? 1 : 0) | (a.zcolmax ? 2 : 0);
-        if (cm == 1)
-          return std_ ? launch_c<NT, W, PREC_BF16, true, FAMILY_LOGISTIC, 1>(a, n_chunks, s)
-                      : launch_c<NT, W, PREC_BF16, false, FAMILY_LOGISTIC, 1>(a, n_chunks, s);
-        if (cm == 2)
-          return std_ ? launch_c<NT, W, PREC_BF16, true, FAMILY_LOGISTIC, 2>(a, n_chunks, s)
-                      : launch_c<NT, W, PREC_BF16, false, FAMILY_LOGISTIC, 2>(a, n_chunks, s);
-        if (cm == 3)
-          return std_ ? launch_c<NT, W, PREC_BF16, true, FAMILY_LOGISTIC, 3>(a, n_chunks, s)
-                      : launch_c<NT, W, PREC_BF16, false, FAMILY_LOGISTIC, 3>(a, n_chunks, s);
-      }
-      return std_ ? launch_c<NT, W, PREC_BF16, true, FAMILY_LOGISTIC>(a, n_chunks, s)
-                  : launch_c<NT, W, PREC_BF16, false, FAMILY_LOGISTIC>(a, n_chunks, s);
-    case PREC_F32:
-      return std_ ? launch_c<NT, W, PREC_F32, true, FAMILY_LOGISTIC>(a, n_chunks, s)
-                  : launch_c<NT, W, PREC_F32, false, FAMILY_LOGISTIC>(a, n_chunks, s);
-    default:
-      return std_ ? launch_c<NT, W, PREC_F64, true, FAMILY_LOGISTIC>(a, n_chunks, s)
-                  : launch_c<NT, W, PREC_F64, false, FAMILY_LOGISTIC>(a, n_chunks, s);
-  }
-}
+template <int V>
+using int_c = std::integral_constant<int, V>;
 
-// Poisson family: never records digit scales (CM = 0: no int8 exact pass).
-// Instantiated by the irls_coop_pois_g*.hip units only; OFS (PassArgsOfs,
-// eta_offset set) by the irls_coop_pois_ofs_g*.hip units only.
-template <int NT, bool OFS = false>
-static hipError_t launch_coop_poisson_nt(const typename pass_args_of<OFS>::type& a, int prec,
-                                         bool std_, int n_chunks, hipStream_t s) {
+// The launcher of one (NT, family, offset): the precision, CM and
+// standardisation selection, each arm guarded by the family's rules, so a
+// unit instantiates the kernels its families may launch and no other (no CM
+// kernel without digit scales or above kOzMaxNT, one precision for a family
+// that does not iterate, OFS only with an offset).  A kernel without an
+// offset takes the PassArgs slice of `a`.
+template <int NT, int FAM, bool OFS>
+static hipError_t launch_coop_nt(const PassArgsOfs& a, int prec, bool std_, int n_chunks,
+                                 hipStream_t s) {
+  constexpr FamilyRules R = family_rules(FAM);
   constexpr int W = coop_waves(NT);
-  if (a.colmax || a.zcolmax) return hipErrorInvalidValue;
-  if constexpr (OFS)
-    if (!a.eta_offset) return hipErrorInvalidValue;
-  switch (prec) {
-    case PREC_BF16:
-      return std_ ? launch_c<NT, W, PREC_BF16, true, FAMILY_POISSON, 0, OFS>(a, n_chunks, s)
-                  : launch_c<NT, W, PREC_BF16, false, FAMILY_POISSON, 0, OFS>(a, n_chunks, s);
-    case PREC_F32:
-      return std_ ? launch_c<NT, W, PREC_F32, true, FAMILY_POISSON, 0, OFS>(a, n_chunks, s)
-                  : launch_c<NT, W, PREC_F32, false, FAMILY_POISSON, 0, OFS>(a, n_chunks, s);
-    default:
-      if (!a.slab_llc) return hipErrorInvalidValue;
-      return std_ ? launch_c<NT, W, PREC_F64, true, FAMILY_POISSON, 0, OFS>(a, n_chunks, s)
-                  : launch_c<NT, W, PREC_F64, false, FAMILY_POISSON, 0, OFS>(a, n_chunks, s);
+  static_assert(!OFS || R.offset, "an offset kernel of a family without one");
+  if (!R.iterates && prec != PREC_F64) return hipErrorInvalidValue;
+  if (!R.digit_scales && (a.colmax || a.zcolmax)) return hipErrorInvalidValue;
+  if (R.sums_ll_const && prec == PREC_F64 && !a.slab_llc) return hipErrorInvalidValue;
+  if (OFS && !a.eta_offset) return hipErrorInvalidValue;
+  const typename pass_args_of<OFS>::type& ka = a;
+  auto go = [&](auto prec_c, auto cm_c) {
+    constexpr int PREC = decltype(prec_c)::value, CM = decltype(cm_c)::value;
+    return std_ ? launch_c<NT, W, PREC, true, FAM, CM, OFS>(ka, n_chunks, s)
+                : launch_c<NT, W, PREC, false, FAM, CM, OFS>(ka, n_chunks, s);
+  };
+  if constexpr (R.iterates) {
+    if (prec == PREC_BF16) {
+      if constexpr (R.digit_scales && NT <= kOzMaxNT) {
+        switch ((a.colmax ? 1 : 0) | (a.zcolmax ? 2 : 0)) {
+          case 1: return go(int_c<PREC_BF16>{}, int_c<1>{});
+          case 2: return go(int_c<PREC_BF16>{}, int_c<2>{});
+          case 3: return go(int_c<PREC_BF16>{}, int_c<3>{});
+        }
+      }
+      return go(int_c<PREC_BF16>{}, int_c<0>{});
+    }
+    if (prec == PREC_F32) return go(int_c<PREC_F32>{}, int_c<0>{});
   }
+  return go(int_c<PREC_F64>{}, int_c<0>{});
 }
 
-template <int NT>
-static hipError_t launch_coop_nt(const PassArgs& a, int prec, bool std_, int family,
-                                 int n_chunks, hipStream_t s) {
-  return launch_coop_ntw<NT, coop_waves(NT)>(a, prec, std_, family, n_chunks, s);
-}
+// Entry point of a compilation unit, one line per unit:
+//   DLSA_COOP_UNIT(name, family set (an IntList), OFS, NT...)
+// irls_coop.hip lists the units and routes to them.
+typedef hipError_t CoopUnitFn(const PassArgsOfs& a, int NT, int prec, bool std_, int family,
+                              int n_chunks, hipStream_t s);
+#define DLSA_COOP_UNIT(name, FAMS, OFS, ...)                                                 \
+  hipError_t name(const PassArgsOfs& a, int NT, int prec, bool std_, int family, int n_chunks, \
+                  hipStream_t s) {                                                           \
+    return unit_dispatch(FAMS{}, IntList<__VA_ARGS__>{}, family, NT, [&](auto fam, auto nt) { \
+      return launch_coop_nt<decltype(nt)::value, decltype(fam)::value, OFS>(a, prec, std_,   \
+                                                                            n_chunks, s);    \
+    });                                                                                      \
+  }
 
 }  // namespace dlsa

@@ -3,15 +3,6 @@
 
 namespace dlsa {
 
-hipError_t launch_irls_coop_pois_g3(const PassArgs& a, int NT, int prec, bool std_, int n_chunks,
-                                     hipStream_t s) {
-  switch (NT) {
-    case 9: return launch_coop_poisson_nt<9>(a, prec, std_, n_chunks, s);
-    case 10: return launch_coop_poisson_nt<10>(a, prec, std_, n_chunks, s);
-    case 11: return launch_coop_poisson_nt<11>(a, prec, std_, n_chunks, s);
-    case 12: return launch_coop_poisson_nt<12>(a, prec, std_, n_chunks, s);
-    default: return hipErrorInvalidValue;
-  }
-}
+DLSA_COOP_UNIT(launch_irls_coop_pois_g3, FamPoisson, false, 9, 10, 11, 12)
 
 }  // namespace dlsa

@@ -1,28 +1,32 @@
-// Ozaki-scheme exact pass (irls_oz_impl.hpp): host entry point; NT = 7 is
-// instantiated in irls_oz_g2.hip so the two halves compile in parallel.
+// Ozaki-scheme exact pass (irls_oz_impl.hpp): host entry point and the table
+// of its units; NT = 7 is instantiated in irls_oz_g2.hip so the two halves
+// compile in parallel.
 #include "irls_oz_impl.hpp"
 
 namespace dlsa {
 
-hipError_t launch_irls_oz_g2(const PassArgs& a, int NT, bool std_, int n_chunks, hipStream_t s);
+// entry point, families, offset, first and last NT
+#define DLSA_OZ_UNITS(U)                         \
+  U(launch_irls_oz_g1, FamLogistic, false, 1, 6) \
+  U(launch_irls_oz_g2, FamLogistic, false, 7, 7)
+#define DLSA_DECLARE(name, fams, ofs, lo, hi) OzUnitFn name;
+#define DLSA_ROW(name, fams, ofs, lo, hi) {fams::mask, ofs, lo, hi, name},
+DLSA_OZ_UNITS(DLSA_DECLARE)
+static const UnitRow<OzUnitFn> kOzUnits[] = {DLSA_OZ_UNITS(DLSA_ROW)};
+
+DLSA_OZ_UNIT(launch_irls_oz_g1, 1, 2, 3, 4, 5, 6)
 
 bool oz_applies(int NT, int p) { return NT >= 1 && NT <= kOzMaxNT && ozk::fits(NT, p); }
 
-// Logistic only: the pass takes its digit scales from the records of a
-// full-data approximate pass, which a Gaussian fit (one exact pass) never runs.
+// Only a family with digit scales: the pass takes them from the records of a
+// full-data approximate pass, which a Gaussian fit (one exact pass) never runs
+// and a Poisson fit (unbounded weights) does not record.
 hipError_t launch_irls_oz(const PassArgs& a, int NT, bool standardize, int family, int n_chunks,
                           hipStream_t s) {
-  if (family != FAMILY_LOGISTIC) return hipErrorInvalidValue;
+  if (!family_rules(family).digit_scales) return hipErrorInvalidValue;
   if (!oz_applies(NT, a.p) || !a.colmax || !a.zcolmax || !a.theta_rec) return hipErrorInvalidValue;
-  switch (NT) {
-    case 1: return launch_oz_nt<1>(a, standardize, n_chunks, s);
-    case 2: return launch_oz_nt<2>(a, standardize, n_chunks, s);
-    case 3: return launch_oz_nt<3>(a, standardize, n_chunks, s);
-    case 4: return launch_oz_nt<4>(a, standardize, n_chunks, s);
-    case 5: return launch_oz_nt<5>(a, standardize, n_chunks, s);
-    case 6: return launch_oz_nt<6>(a, standardize, n_chunks, s);
-    default: return launch_irls_oz_g2(a, NT, standardize, n_chunks, s);
-  }
+  OzUnitFn* unit = find_unit(kOzUnits, family, false, NT);
+  return unit ? unit(a, NT, standardize, family, n_chunks, s) : hipErrorInvalidValue;
 }
 
 }  // namespace dlsa

@@ -4,12 +4,7 @@
 
 namespace dlsa {
 
-hipError_t launch_irls_oz_g2(const PassArgs& a, int NT, bool std_, int n_chunks, hipStream_t s) {
-  switch (NT) {
-    case 7: return launch_oz_nt<7>(a, std_, n_chunks, s);
-    default: return hipErrorInvalidValue;
-  }
-}
+DLSA_OZ_UNIT(launch_irls_oz_g2, 7)
 
 }  // namespace dlsa
 

@@ -271,7 +271,7 @@ struct OzConsumer {
   oz_i4 acc[TW > 0 ? TW : 1][ozk::NL];
 
   __device__ __forceinline__ void init() {
-    wv_static_for<(TW > 0 ? TW : 1)>([&](auto iI) {
+    static_for<(TW > 0 ? TW : 1)>([&](auto iI) {
       constexpr int i = decltype(iI)::value;
 #pragma unroll
       for (int k = 0; k < ozk::NL; ++k) acc[i][k] = oz_i4{0, 0, 0, 0};
@@ -306,7 +306,7 @@ struct OzConsumer {
       };
       loadB(std::integral_constant<int, TL::J_of(0)>{}, 0);
       loadA(std::integral_constant<int, 0>{}, 0);
-      wv_static_for<TW>([&](auto tI) {
+      static_for<TW>([&](auto tI) {
         constexpr int t = decltype(tI)::value;
         constexpr int J = TL::J_of(t);
         constexpr int ua = t & 1;
@@ -340,7 +340,7 @@ struct OzConsumer {
         tick(std::integral_constant<int, t>{});
       });
       // keep the level accumulators in registers across the loop
-      wv_static_for<TW>([this](auto iI) {
+      static_for<TW>([this](auto iI) {
         constexpr int t = decltype(iI)::value;
 #pragma unroll
         for (int k = 0; k < ozk::NL; ++k) asm volatile("" : "+v"(acc[t][k]));
@@ -352,7 +352,7 @@ struct OzConsumer {
   __device__ __forceinline__ void store(double* sH, const int* ex, int lane) {
     if constexpr (TW > 0) {
       const int fl = lane & 15, q = lane >> 4;
-      wv_static_for<TW>([&](auto iI) {
+      static_for<TW>([&](auto iI) {
         constexpr int t = decltype(iI)::value;
         constexpr int I = TL::I_of(t), J = TL::J_of(t);
         constexpr int ts = I * (I + 1) / 2 + J;
@@ -415,11 +415,11 @@ __device__ __forceinline__ void oz_producer(const PassArgs& a, char* smem, int w
   // waits for its own pieces before the next barrier, which then publishes
   // all of them
   issue_pair(-1);
-  wv_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   OZ_DECL;
   for (int m = 0; m < nit; ++m) {
     OZ_STAMP(t0);
-    wv_wait_vmcnt<0>();
+    wait_vmcnt<0>();
     lds_barrier();  // B_m
     OZ_STAMP(t1);
     OZ_ADD(0, t1 - t0);
@@ -597,9 +597,7 @@ __global__ __launch_bounds__(64 * (ozk::NPW + ozk::NCW), 1) void irls_oz_kernel(
   const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int p = a.p, P = a.P, ic = a.intercept;
-  const int64_t row0 =
-      ((int64_t)__builtin_amdgcn_readfirstlane((int)(a.chunk_row0[chunk] >> 32)) << 32) |
-      (uint32_t)__builtin_amdgcn_readfirstlane((int)a.chunk_row0[chunk]);
+  const int64_t row0 = uniform_row0(a.chunk_row0, chunk);
   const int nrows = __builtin_amdgcn_readfirstlane(a.chunk_rows[chunk]);
   const int nb = (nrows + RB - 1) / RB;
   const int nit = (nb + 1) / 2 + 1;  // iterations (the last only consumes)
@@ -703,18 +701,18 @@ __global__ __launch_bounds__(64 * (ozk::NPW + ozk::NCW), 1) void irls_oz_kernel(
     if (i < npw) {  // uniform
       const int j = dw + NCW * i;
       const int off = j == np - 1 ? xs_bytes - 1024 : j * 1024;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (wlds_void_t*)(smem + lds + 16 + off), 16,
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_void_t*)(smem + lds + 16 + off), 16,
                                                lane * 16, soff + off, 0, DLSA_OZ_DMA_AUX);
     }
   };
   auto issue_y = [&](int blk, int lds) {
     if (dw == NCW - 1)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(yr, (wlds_void_t*)(smem + lds + 16 + xs_bytes), 4,
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(yr, (lds_void_t*)(smem + lds + 16 + xs_bytes), 4,
                                                lane * 4, blk * RB * 8, 0, 0);
   };
   // the consumers' share: a block's pieces from piece I0 on, and its y
   auto issue_rest = [&](auto I0, int blk, int lds, int soff) {
-    wv_static_for<kMaxPiecesPerWave>([&](auto iI) {
+    static_for<kMaxPiecesPerWave>([&](auto iI) {
       if constexpr (decltype(iI)::value >= decltype(I0)::value) issue_x(iI, lds, soff);
     });
     issue_y(blk, lds);
@@ -743,7 +741,7 @@ __global__ __launch_bounds__(64 * (ozk::NPW + ozk::NCW), 1) void irls_oz_kernel(
       C.init();
       for (int b = 0; b < 2 && b < nb; ++b)
         issue_rest(std::integral_constant<int, KP>{}, b, blk_lds(b), blk_soff(b));
-      wv_wait_vmcnt<0>();
+      wait_vmcnt<0>();
       OZ_DECL;
       for (int m = 0; m < nit; ++m) {
         OZ_STAMP(t0);
@@ -775,7 +773,7 @@ __global__ __launch_bounds__(64 * (ozk::NPW + ozk::NCW), 1) void irls_oz_kernel(
         if (c1) C.consume(slot_x(2 * m - 1), p, lane, tickN);
         OZ_STAMP_SET(t2);
         OZ_STAMP(t3);
-        wv_wait_vmcnt<0>();
+        wait_vmcnt<0>();
         OZ_STAMP(t4);
         OZ_ADD(0, t1 - t0);
         OZ_ADD(1, t3 - t2);
@@ -814,5 +812,16 @@ template <int NT>
 static hipError_t launch_oz_nt(const PassArgs& a, bool std_, int n_chunks, hipStream_t s) {
   return std_ ? launch_oz_t<NT, true>(a, n_chunks, s) : launch_oz_t<NT, false>(a, n_chunks, s);
 }
+
+// Entry point of a compilation unit, one line per unit (the family with digit
+// scales only): DLSA_OZ_UNIT(name, NT...); irls_oz.hip routes to them.
+typedef hipError_t OzUnitFn(const PassArgs& a, int NT, bool std_, int family, int n_chunks,
+                            hipStream_t s);
+#define DLSA_OZ_UNIT(name, ...)                                                                  \
+  hipError_t name(const PassArgs& a, int NT, bool std_, int family, int n_chunks, hipStream_t s) { \
+    return unit_dispatch(FamLogistic{}, IntList<__VA_ARGS__>{}, family, NT, [&](auto, auto nt) { \
+      return launch_oz_nt<decltype(nt)::value>(a, std_, n_chunks, s);                            \
+    });                                                                                          \
+  }
 
 }  // namespace dlsa

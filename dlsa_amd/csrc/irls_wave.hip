@@ -1,22 +1,25 @@
-// Per-wave fp64 IRLS pass: host entry point (kernel in irls_wave_impl.hpp;
-// NT = 7, 8 are instantiated in irls_wave_g2.hip so the two halves compile in
-// parallel).
+// Per-wave fp64 IRLS pass: host entry point and the table of the units that
+// hold the kernels (irls_wave_impl.hpp; one DLSA_WAVE_UNIT line each: NT 1..6
+// of the logistic and Gaussian families here, the others in irls_wave_*.hip,
+// so they compile in parallel).
 #include "irls_wave_impl.hpp"
 
 namespace dlsa {
 
-hipError_t launch_irls_wave_g2(const PassArgs& a, int NT, bool std_, int family, int n_chunks,
-                               hipStream_t s);
-// the Poisson family's instantiations (irls_wave_pois_g*.hip)
-hipError_t launch_irls_wave_pois_g1(const PassArgs& a, int NT, bool std_, int n_chunks,
-                                    hipStream_t s);
-hipError_t launch_irls_wave_pois_g2(const PassArgs& a, int NT, bool std_, int n_chunks,
-                                    hipStream_t s);
-// ... with a per-row offset, a.eta_offset set (irls_wave_pois_ofs_g*.hip)
-hipError_t launch_irls_wave_pois_ofs_g1(const PassArgsOfs& a, int NT, bool std_, int n_chunks,
-                                        hipStream_t s);
-hipError_t launch_irls_wave_pois_ofs_g2(const PassArgsOfs& a, int NT, bool std_, int n_chunks,
-                                        hipStream_t s);
+// entry point, families, offset, first and last NT
+#define DLSA_WAVE_UNITS(U)                                     \
+  U(launch_irls_wave_g1, FamLogisticGaussian, false, 1, 6)     \
+  U(launch_irls_wave_g2, FamLogisticGaussian, false, 7, 8)     \
+  U(launch_irls_wave_pois_g1, FamPoisson, false, 1, 6)         \
+  U(launch_irls_wave_pois_g2, FamPoisson, false, 7, 8)         \
+  U(launch_irls_wave_pois_ofs_g1, FamPoisson, true, 1, 6)      \
+  U(launch_irls_wave_pois_ofs_g2, FamPoisson, true, 7, 8)
+#define DLSA_DECLARE(name, fams, ofs, lo, hi) WaveUnitFn name;
+#define DLSA_ROW(name, fams, ofs, lo, hi) {fams::mask, ofs, lo, hi, name},
+DLSA_WAVE_UNITS(DLSA_DECLARE)
+static const UnitRow<WaveUnitFn> kWaveUnits[] = {DLSA_WAVE_UNITS(DLSA_ROW)};
+
+DLSA_WAVE_UNIT(launch_irls_wave_g1, FamLogisticGaussian, false, 1, 2, 3, 4, 5, 6)
 
 // (the logistic ring is the larger one; the Poisson pass has its geometry)
 int wave_lds_bytes(int NT, int p) {
@@ -25,22 +28,9 @@ int wave_lds_bytes(int NT, int p) {
 
 hipError_t launch_irls_wave(const PassArgsOfs& a, int NT, bool standardize, int family,
                             int n_chunks, hipStream_t s) {
-  if (a.eta_offset && family != FAMILY_POISSON) return hipErrorInvalidValue;
-  if (family == FAMILY_POISSON && a.eta_offset)
-    return NT <= 6 ? launch_irls_wave_pois_ofs_g1(a, NT, standardize, n_chunks, s)
-                   : launch_irls_wave_pois_ofs_g2(a, NT, standardize, n_chunks, s);
-  if (family == FAMILY_POISSON)
-    return NT <= 6 ? launch_irls_wave_pois_g1(a, NT, standardize, n_chunks, s)
-                   : launch_irls_wave_pois_g2(a, NT, standardize, n_chunks, s);
-  switch (NT) {
-    case 1: return launch_wave_nt<1>(a, standardize, family, n_chunks, s);
-    case 2: return launch_wave_nt<2>(a, standardize, family, n_chunks, s);
-    case 3: return launch_wave_nt<3>(a, standardize, family, n_chunks, s);
-    case 4: return launch_wave_nt<4>(a, standardize, family, n_chunks, s);
-    case 5: return launch_wave_nt<5>(a, standardize, family, n_chunks, s);
-    case 6: return launch_wave_nt<6>(a, standardize, family, n_chunks, s);
-    default: return launch_irls_wave_g2(a, NT, standardize, family, n_chunks, s);
-  }
+  if (a.eta_offset && !family_rules(family).offset) return hipErrorInvalidValue;
+  WaveUnitFn* unit = find_unit(kWaveUnits, family, a.eta_offset != nullptr, NT);
+  return unit ? unit(a, NT, standardize, family, n_chunks, s) : hipErrorInvalidValue;
 }
 
 }  // namespace dlsa

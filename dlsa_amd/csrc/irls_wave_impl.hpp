@@ -41,15 +41,8 @@
 namespace dlsa {
 
 typedef double wd4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void wlds_void_t;
 
 namespace {
-
-template <int N>
-__device__ __forceinline__ void wv_wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits on gfx950");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 __device__ __forceinline__ double wv_xor16(double v) {
   const unsigned lo = __double2loint(v), hi = __double2hiint(v);
@@ -253,15 +246,6 @@ struct WaveTiles {
   }
 };
 
-template <typename F, int... Is>
-__device__ __forceinline__ void wv_static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void wv_static_for(F&& f) {
-  wv_static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 // workgroup sync of the block loop: this wave's LDS ops done, then (W > 1) a
 // barrier without the vmcnt drain of __syncthreads (the next block's DMA
 // stays in flight; lds_barrier)
@@ -339,14 +323,14 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
     const uintptr_t start = (uintptr_t)(a.X + (cx.row0 + (int64_t)blk * RB) * p);
     const int so = __builtin_amdgcn_readfirstlane((int)((start & ~(uintptr_t)15) - cx.xcb));
     for (int j = WID; j < cx.npieces; j += W)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.xr, (wlds_void_t*)(sbase + 16 + j * 1024), 16,
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.xr, (lds_void_t*)(sbase + 16 + j * 1024), 16,
                                                lane * 16, so + j * 1024, 0, DLSA_X_DMA_AUX);
     if (WID == W - 1)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.yr, (wlds_void_t*)(sbase + cx.slot_y), 4,
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.yr, (lds_void_t*)(sbase + cx.slot_y), 4,
                                                lane * 4, blk * RB * 8, 0, 0);
     if constexpr (OFS)
       if (WID == W - 1)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.orr, (wlds_void_t*)(sbase + cx.slot_y + 256),
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.orr, (lds_void_t*)(sbase + cx.slot_y + 256),
                                                  4, lane * 4, blk * RB * 8, 0, 0);
   };
 
@@ -355,7 +339,7 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
   for (int b = 0; b < kWaveSlots - 1 && b < cx.nb; ++b) issue(b);
   for (int b = 0; b < cx.nb; ++b) {
     static_assert(kWaveSlots == 2, "one block in flight: the wait is for all of this wave's DMA");
-    wv_wait_vmcnt<0>();  // this wave's pieces of block b landed
+    wait_vmcnt<0>();  // this wave's pieces of block b landed
     wv_sync<W>();        // every wave's pieces landed; block b-1 fully consumed
     if (b + kWaveSlots - 1 < cx.nb) issue(b + kWaveSlots - 1);  // into the slot of block b-1
     const char* slot = smem + (b % kWaveSlots) * cx.slot_bytes;
@@ -473,7 +457,7 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
         for (int r = 0; r < NS; ++r) as[r] = OLS_NOMUL ? xso[u][r] : xso[u][r] * wk[u];
       }
       // tiles in row order: a row's A operand is reused back to back
-      wv_static_for<TW>([&](auto iI) {
+      static_for<TW>([&](auto iI) {
         constexpr int i = decltype(iI)::value;
         constexpr int I = TL::I_of(i), J = TL::J_of(i);
         if constexpr (strip(I)) {
@@ -489,16 +473,16 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
     // strip's 64-bit ones are left to the allocator: pinned one by one they
     // get shuffled between AGPRs; explicit capture: an asm operand alone does
     // not capture in a generic lambda)
-    wv_static_for<TW>([&acc](auto iI) {
+    static_for<TW>([&acc](auto iI) {
       constexpr int i = decltype(iI)::value;
       if constexpr (!(NS > 0 && TL::I_of(i) == NT - 1)) asm volatile("" : "+a"(acc[i]));
     });
   }
-  wv_wait_vmcnt<0>();
+  wait_vmcnt<0>();
 
   // ---- epilogue: this chunk's partials (newton_solve.hip slab layout) --------
   double* sH = a.slab_H + (int64_t)cx.chunk * (NT * (NT + 1) / 2) * 256;
-  wv_static_for<TW>([&](auto iI) {
+  static_for<TW>([&](auto iI) {
     constexpr int i = decltype(iI)::value;
     constexpr int t = TL::I_of(i) * (TL::I_of(i) + 1) / 2 + TL::J_of(i);
 #pragma unroll
@@ -580,8 +564,7 @@ __global__ __launch_bounds__(64 * W, wave_min_waves(NT, W, FAM)) void irls_wave_
 
   const int tid = threadIdx.x;
   const int p = a.p, P = a.P, ic = a.intercept;
-  cx.row0 = ((int64_t)__builtin_amdgcn_readfirstlane((int)(a.chunk_row0[cx.chunk] >> 32)) << 32) |
-            (uint32_t)__builtin_amdgcn_readfirstlane((int)a.chunk_row0[cx.chunk]);
+  cx.row0 = uniform_row0(a.chunk_row0, cx.chunk);
   cx.nrows = __builtin_amdgcn_readfirstlane(a.chunk_rows[cx.chunk]);
   cx.nb = (cx.nrows + RB - 1) / RB;
   cx.npieces = wave_npieces(RB, p);
@@ -662,27 +645,31 @@ static hipError_t launch_wave_sf(const typename pass_args_of<OFS>::type& a, int 
   return launch_wave_t<NT, 1, STD, FAM, OFS>(a, n_chunks, s);
 }
 
-template <int NT>
-static hipError_t launch_wave_nt(const PassArgs& a, bool std_, int family, int n_chunks,
-                                 hipStream_t s) {
-  if (family == FAMILY_GAUSSIAN)
-    return std_ ? launch_wave_sf<NT, true, FAMILY_GAUSSIAN>(a, n_chunks, s)
-                : launch_wave_sf<NT, false, FAMILY_GAUSSIAN>(a, n_chunks, s);
-  if (family == FAMILY_POISSON) return hipErrorInvalidValue;  // launch_wave_poisson_nt
-  return std_ ? launch_wave_sf<NT, true, FAMILY_LOGISTIC>(a, n_chunks, s)
-              : launch_wave_sf<NT, false, FAMILY_LOGISTIC>(a, n_chunks, s);
+// The launcher of one (NT, family, offset), guarded by the family's rules.  A
+// kernel without an offset takes the PassArgs slice of `a`.
+template <int NT, int FAM, bool OFS>
+static hipError_t launch_wave_nt(const PassArgsOfs& a, bool std_, int n_chunks, hipStream_t s) {
+  constexpr FamilyRules R = family_rules(FAM);
+  static_assert(!OFS || R.offset, "an offset kernel of a family without one");
+  if (R.sums_ll_const && !a.slab_llc) return hipErrorInvalidValue;
+  if (OFS && !a.eta_offset) return hipErrorInvalidValue;
+  const typename pass_args_of<OFS>::type& ka = a;
+  return std_ ? launch_wave_sf<NT, true, FAM, OFS>(ka, n_chunks, s)
+              : launch_wave_sf<NT, false, FAM, OFS>(ka, n_chunks, s);
 }
 
-// Poisson family (instantiated by the irls_wave_pois_g*.hip units only; OFS,
-// PassArgsOfs with eta_offset set, by the irls_wave_pois_ofs_g*.hip units only)
-template <int NT, bool OFS = false>
-static hipError_t launch_wave_poisson_nt(const typename pass_args_of<OFS>::type& a, bool std_,
-                                         int n_chunks, hipStream_t s) {
-  if (!a.slab_llc) return hipErrorInvalidValue;
-  if constexpr (OFS)
-    if (!a.eta_offset) return hipErrorInvalidValue;
-  return std_ ? launch_wave_sf<NT, true, FAMILY_POISSON, OFS>(a, n_chunks, s)
-              : launch_wave_sf<NT, false, FAMILY_POISSON, OFS>(a, n_chunks, s);
-}
+// Entry point of a compilation unit, one line per unit:
+//   DLSA_WAVE_UNIT(name, family set (an IntList), OFS, NT...)
+// irls_wave.hip lists the units and routes to them.
+typedef hipError_t WaveUnitFn(const PassArgsOfs& a, int NT, bool std_, int family, int n_chunks,
+                              hipStream_t s);
+#define DLSA_WAVE_UNIT(name, FAMS, OFS, ...)                                                  \
+  hipError_t name(const PassArgsOfs& a, int NT, bool std_, int family, int n_chunks,          \
+                  hipStream_t s) {                                                            \
+    return unit_dispatch(FAMS{}, IntList<__VA_ARGS__>{}, family, NT, [&](auto fam, auto nt) { \
+      return launch_wave_nt<decltype(nt)::value, decltype(fam)::value, OFS>(a, std_, n_chunks, \
+                                                                            s);               \
+    });                                                                                       \
+  }
 
 }  // namespace dlsa

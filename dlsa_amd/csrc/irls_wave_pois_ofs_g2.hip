@@ -4,13 +4,6 @@
 
 namespace dlsa {
 
-hipError_t launch_irls_wave_pois_ofs_g2(const PassArgsOfs& a, int NT, bool std_, int n_chunks,
-                                         hipStream_t s) {
-  switch (NT) {
-    case 7: return launch_wave_poisson_nt<7, true>(a, std_, n_chunks, s);
-    case 8: return launch_wave_poisson_nt<8, true>(a, std_, n_chunks, s);
-    default: return hipErrorInvalidValue;
-  }
-}
+DLSA_WAVE_UNIT(launch_irls_wave_pois_ofs_g2, FamPoisson, true, 7, 8)
 
 }  // namespace dlsa

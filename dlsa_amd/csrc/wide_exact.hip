@@ -337,7 +337,7 @@ __global__ __launch_bounds__(256) void wide_assemble_kernel(const WideArgs a, co
 // ---------------------------------------------------------------------------
 template <int MB, bool STD>
 static hipError_t launch_row_t(const WideArgs& a, int family, int n_chunks, hipStream_t s) {
-  if (family == FAMILY_GAUSSIAN)
+  if (!family_rules(family).iterates)  // the closed form: w = 1
     hipLaunchKernelGGL((wide_row_kernel<MB, STD, FAMILY_GAUSSIAN>), dim3(n_chunks), dim3(256), 0,
                        s, a);
   else

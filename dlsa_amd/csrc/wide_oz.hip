@@ -179,7 +179,7 @@ __global__ __launch_bounds__(512, 1) void wide_oz_gram_kernel(const WideArgs a, 
                              : 32 * PP + (ab ? J : I) * kOzGT * 8;
       const int soff = s * stepb + j * PP * kRec + src;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          dr, (wlds_void_t*)(st + ab * kPanel + j * kOzGT * kRec + e * 1024), 16, lane * 16,
+          dr, (lds_void_t*)(st + ab * kPanel + j * kOzGT * kRec + e * 1024), 16, lane * 16,
           __builtin_amdgcn_readfirstlane(soff), 0, 0);
     }
   };
@@ -195,9 +195,9 @@ __global__ __launch_bounds__(512, 1) void wide_oz_gram_kernel(const WideArgs a, 
   issue(0);
   if (nsteps > 1) issue(1);
   if (nsteps > 1)
-    wv_wait_vmcnt<5>();
+    wait_vmcnt<5>();
   else
-    wv_wait_vmcnt<0>();
+    wait_vmcnt<0>();
   lds_barrier();
   for (int s = 0; s < nsteps; ++s) {
     if (s + 2 < nsteps) issue(s + 2);
@@ -244,9 +244,9 @@ __global__ __launch_bounds__(512, 1) void wide_oz_gram_kernel(const WideArgs a, 
     }
     // step s+1 landed (s+2 may stay in flight); everyone done with stage s
     if (s + 2 < nsteps)
-      wv_wait_vmcnt<5>();
+      wait_vmcnt<5>();
     else
-      wv_wait_vmcnt<0>();
+      wait_vmcnt<0>();
     lds_barrier();  // (not __syncthreads: its fence would drain step s+2's DMA)
   }
   if (idle) return;
