@@ -364,6 +364,20 @@ void irls_coop_kernel(const typename pass_args_of<OFS>::type a) {
     const double* xs = (const double*)(slot + G::PAD + (start & 15));
     const double* ys = (const double*)(slot + slot_x);
     const int rows_left = nrows - b * RB;
+    // The chunk's last block: its rows past the chunk's end, and the PMAX
+    // doubles behind the block that the last row's lanes of the padded
+    // features f >= P read, are the next chunk's rows (another partition's,
+    // possibly non-finite) or the bytes after X up to its 16-byte boundary.
+    // They carry w = r = 0 and beta = 0, but 0 * NaN is NaN: zero them in the
+    // slot, for the row phase and the tile phase alike.  (No DMA is in flight
+    // to this slot: the tail re-fetches go to the other slots.)
+    if (__builtin_expect(b == nb - 1, 0)) {  // workgroup-uniform
+      double* zs = (double*)(smem + (b % nslot) * slot_bytes + G::PAD + (start & 15));
+      zs += rows_left * p;
+      const int nz = (RB - rows_left) * p + G::PMAX;
+      for (int i = tid; i < nz; i += 64 * W) zs[i] = 0.0;
+      lds_barrier();
+    }
 
     // ---- B: row phase ------------------------------------------------------
     if constexpr (DLSA_ABLATE != 3 && DLSA_ABLATE != 4) {

@@ -347,6 +347,17 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
     double* xs = (double*)(slot + 16 + (start & 15));
     const double* ys = (const double*)(slot + cx.slot_y);
     const int rows_left = cx.nrows - b * RB;
+    // The chunk's last block: rows past the chunk's end and what the last
+    // row's padded-feature lanes read behind the block (the next chunk's rows,
+    // or the bytes after X up to its 16-byte boundary) are zeroed in the slot
+    // -- w = 0 does not keep a NaN out (0 * NaN) -- up to the slot's y.
+    if (__builtin_expect(b == cx.nb - 1, 0)) {  // workgroup-uniform; no DMA in flight to this slot
+      double* zs = xs + rows_left * p;
+      const int lim = (cx.npieces * 1024 - (int)(start & 15)) / 8;  // doubles of X bytes in the slot
+      const int nz = min(RB * p + PMAX, lim) - rows_left * p;
+      for (int i = WID * 64 + lane; i < nz; i += 64 * W) zs[i] = 0.0;
+      wv_sync<W>();
+    }
 
     // ---- row phase: RW rows of this wave, LPR lanes per row -------------------
     {

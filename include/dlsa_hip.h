@@ -27,7 +27,7 @@
  *     "partition_id") + groupby produce per task, projects/logistic_dlsa.py:
  *     303-325).  X must be readable up to the next 16-byte boundary past its
  *     last element (true for any torch/hipMalloc allocation that starts at
- *     the tensor).
+ *     the tensor); what those bytes hold does not matter.
  *   - P = p + fit_intercept is the parameter count; with an intercept the
  *     intercept is parameter 0 (dlsa/models.py:116-122).
  */
