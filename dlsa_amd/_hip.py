@@ -103,6 +103,19 @@ SIGNATURES = {
          ctypes.POINTER(FitOptions), _P]),
     "dlsa_poisson_loglik_batched_sum_offset": (
         ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
+    # the weighted entries: row_weight [n] after y (Poisson: after eta_offset)
+    "dlsa_logistic_fit_batched_weighted": (
+        ctypes.c_int,
+        [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _F64, _P, _P, _P, _P, _P, _P,
+         ctypes.POINTER(FitOptions), _P]),
+    "dlsa_poisson_fit_batched_weighted": (
+        ctypes.c_int,
+        [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _F64, _P, _P, _P, _P, _P, _P,
+         ctypes.POINTER(FitOptions), _P]),
+    "dlsa_logistic_loglik_batched_sum_weighted": (
+        ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
+    "dlsa_poisson_loglik_batched_sum_weighted": (
+        ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
     "dlsa_ols_fit_batched": (
         ctypes.c_int,
         [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(FitOptions),

@@ -193,6 +193,107 @@ hipError_t launch_poisson_start(const double* y, const int64_t* offsets_dev, int
   return hipGetLastError();
 }
 
+// Pre-pass of a weighted fit, after fit_init: the fixed-order sum of
+// poisson_start_kernel over the partition's prior weights omega (and, for
+// Poisson, over omega y and omega exp(o); o = 0 without an offset).  A
+// negative or non-finite omega ends the partition NONFINITE and sum omega = 0
+// SINGULAR, before any pass and with the zeroed outputs fit_init wrote;
+// nothing per row is stored.
+//   POISSON: also the checks of the unweighted start (y, o), sum omega y = 0
+//   ends the partition SINGULAR, and with an intercept the fit starts at
+//   theta = (log(sum omega y / sum omega exp(o)), 0, ..., 0), the MLE of the
+//   weighted intercept-only model (theta0[k] keeps it for the restarts).
+//   Logistic: statuses only; the start stays theta = 0.
+template <bool POISSON>
+__global__ __launch_bounds__(256) void weight_start_kernel(
+    const double* y, const double* eta_offset, const double* row_weight, const int64_t* offsets,
+    int P, int intercept, double* theta, double* theta0, int32_t* phase, int32_t* status) {
+  __shared__ double ssw[4], sswy[4], sswe[4], smin[4];
+  __shared__ int sbad[4];
+  const int k = blockIdx.x;
+  const int64_t r0 = offsets[k], r1 = offsets[k + 1];
+  double sw = 0.0, swy = 0.0, swe = 0.0, mn = INFINITY;  // mn: min over omega (and y)
+  int bad = 0;
+  for (int64_t i = r0 + threadIdx.x; i < r1; i += 256) {
+    const double om = row_weight[i];
+    bad |= !isfinite(om);
+    sw += om;
+    mn = fmin(mn, om);
+    if constexpr (POISSON) {
+      const double v = y[i];
+      bad |= !isfinite(v);
+      mn = fmin(mn, v);
+      swy += om * v;
+      if (eta_offset) {
+        const double o = eta_offset[i];
+        bad |= !isfinite(o);
+        swe += om * exp(o);
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sw += __shfl_xor(sw, o);
+    swy += __shfl_xor(swy, o);
+    swe += __shfl_xor(swe, o);
+    mn = fmin(mn, __shfl_xor(mn, o));
+    bad |= __shfl_xor(bad, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    ssw[threadIdx.x >> 6] = sw;
+    sswy[threadIdx.x >> 6] = swy;
+    sswe[threadIdx.x >> 6] = swe;
+    smin[threadIdx.x >> 6] = mn;
+    sbad[threadIdx.x >> 6] = bad;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  sw = ((ssw[0] + ssw[1]) + ssw[2]) + ssw[3];
+  swy = ((sswy[0] + sswy[1]) + sswy[2]) + sswy[3];
+  swe = ((sswe[0] + sswe[1]) + sswe[2]) + sswe[3];
+  mn = fmin(fmin(smin[0], smin[1]), fmin(smin[2], smin[3]));
+  bad = sbad[0] | sbad[1] | sbad[2] | sbad[3];
+  if constexpr (POISSON) {
+    theta0[k] = 0.0;
+    if (!eta_offset) swe = sw;
+  }
+  if (r1 <= r0) return;  // empty: fit_init's DLSA_STATUS_EMPTY stands
+  if (bad || !(mn >= 0.0) || !isfinite(sw) || !isfinite(swy) || !isfinite(swe)) {
+    status[k] = DLSA_STATUS_NONFINITE;
+    phase[k] = PHASE_DONE;
+  } else if (!(sw > 0.0) || (POISSON && !(swy > 0.0))) {
+    status[k] = DLSA_STATUS_SINGULAR;
+    phase[k] = PHASE_DONE;
+  } else if constexpr (POISSON) {
+    if (!(swe > 0.0) || !isfinite(swy / swe)) {  // no finite start exists
+      status[k] = DLSA_STATUS_NONFINITE;
+      phase[k] = PHASE_DONE;
+    } else if (intercept) {
+      const double t0 = log(swy / swe);
+      theta0[k] = t0;
+      theta[(int64_t)k * P] = t0;
+    }
+  }
+}
+
+hipError_t launch_weight_check(const double* row_weight, const int64_t* offsets_dev, int K,
+                               int32_t* phase, int32_t* status, hipStream_t s) {
+  if (K <= 0) return hipSuccess;
+  hipLaunchKernelGGL(weight_start_kernel<false>, dim3(K), dim3(256), 0, s, nullptr, nullptr,
+                     row_weight, offsets_dev, 0, 0, nullptr, nullptr, phase, status);
+  return hipGetLastError();
+}
+
+hipError_t launch_poisson_start_wgt(const double* y, const double* eta_offset,
+                                    const double* row_weight, const int64_t* offsets_dev, int K,
+                                    int P, int intercept, double* theta, double* theta0,
+                                    int32_t* phase, int32_t* status, hipStream_t s) {
+  if (K <= 0) return hipSuccess;
+  hipLaunchKernelGGL(weight_start_kernel<true>, dim3(K), dim3(256), 0, s, y, eta_offset,
+                     row_weight, offsets_dev, P, intercept, theta, theta0, phase, status);
+  return hipGetLastError();
+}
+
 // Polish pass of a budget that ran out: every still-running partition gets
 // one exact pass at the theta it returns, whose X^T W X is published as
 // Sig_inv -- models.py:114,130 evaluate the weights at whatever coef sklearn

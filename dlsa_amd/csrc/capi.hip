@@ -33,9 +33,9 @@ static int fit_dense(int family, const double* X, const double* y, const int64_t
                      int32_t K, int32_t p, int32_t fit_intercept, const double* center,
                      const double* scale, int32_t max_iter, double tol, const FitOutputs& out,
                      const dlsa_fit_options* opt_in, void* stream,
-                     const double* eta_offset = nullptr) {
+                     const double* eta_offset = nullptr, const double* row_weight = nullptr) {
   DenseFit f{family, X, y, offsets, K, p, fit_intercept, center, scale, max_iter, tol, out,
-             fit_begin(opt_in, stream), eta_offset};
+             fit_begin(opt_in, stream), eta_offset, row_weight};
   int rc = check_offsets(offsets, K);
   if (rc != DLSA_OK) return rc;
   if (p < 0 || (p == 0 && !fit_intercept)) {
@@ -51,6 +51,11 @@ static int fit_dense(int family, const double* X, const double* y, const int64_t
   if (P > rules.max_p) {  // (the Poisson family: fused path only)
     set_error("Poisson fit: P = p + intercept > DLSA_MAX_P_FUSED = " +
               std::to_string(DLSA_MAX_P_FUSED) + " is not supported");
+    return DLSA_E_UNSUPPORTED;
+  }
+  if (row_weight && (!rules.weights || P > DLSA_MAX_P_FUSED)) {  // before any launch
+    set_error("weighted fit: P = p + intercept > DLSA_MAX_P_FUSED = " +
+              std::to_string(DLSA_MAX_P_FUSED) + " (the wide path) is not supported");
     return DLSA_E_UNSUPPORTED;
   }
   rc = check_fit_args(center, scale, out, f.max_iter, f.tol);
@@ -153,6 +158,30 @@ int dlsa_poisson_fit_batched_offset(const double* X, const double* y, const doub
                    eta_offset);
 }
 
+int dlsa_logistic_fit_batched_weighted(const double* X, const double* y, const double* row_weight,
+                                       const int64_t* offsets, int32_t K, int32_t p,
+                                       int32_t fit_intercept, const double* center,
+                                       const double* scale, int32_t max_iter, double tol,
+                                       double* theta, double* sig_inv, double* sig_inv_theta,
+                                       double* loglik, int32_t* iters, int32_t* status,
+                                       const dlsa_fit_options* opt, void* stream) {
+  return fit_dense(FAMILY_LOGISTIC, X, y, offsets, K, p, fit_intercept, center, scale, max_iter,
+                   tol, {theta, sig_inv, sig_inv_theta, loglik, iters, status}, opt, stream,
+                   nullptr, row_weight);
+}
+
+int dlsa_poisson_fit_batched_weighted(const double* X, const double* y, const double* eta_offset,
+                                      const double* row_weight, const int64_t* offsets, int32_t K,
+                                      int32_t p, int32_t fit_intercept, const double* center,
+                                      const double* scale, int32_t max_iter, double tol,
+                                      double* theta, double* sig_inv, double* sig_inv_theta,
+                                      double* loglik, int32_t* iters, int32_t* status,
+                                      const dlsa_fit_options* opt, void* stream) {
+  return fit_dense(FAMILY_POISSON, X, y, offsets, K, p, fit_intercept, center, scale, max_iter,
+                   tol, {theta, sig_inv, sig_inv_theta, loglik, iters, status}, opt, stream,
+                   eta_offset, row_weight);
+}
+
 int dlsa_logistic_fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
                                   const int64_t* offsets, int32_t K, int32_t q, int32_t F,
                                   const int32_t* levels, int32_t fit_intercept,
@@ -203,7 +232,7 @@ static int loglik_dense(int family, const char* entry, const double* X, const do
                         const double* center,
                         const double* scale, const double* betas, int32_t n_beta,
                         double* loglik, double* loglik_sum, void* stream_,
-                        const double* eta_offset = nullptr) {
+                        const double* eta_offset = nullptr, const double* row_weight = nullptr) {
   g_last_error.clear();
   hipStream_t stream = (hipStream_t)stream_;
   int rc = check_offsets(offsets, K);
@@ -235,7 +264,7 @@ static int loglik_dense(int family, const char* entry, const double* X, const do
   double* d_partial = (double*)ws.at(off_partial);
   DLSA_HIP_TRY(upload_eval_plan(pl, K, d_row0, d_rows, d_part, d_pcb, stream));
   if (pl.n_chunks > 0) {
-    EvalArgs ea;
+    EvalArgsWgt ea;  // (the unweighted kernels take its EvalArgs slice)
     memset(&ea, 0, sizeof(ea));
     ea.X = X;
     ea.y = y;
@@ -255,11 +284,16 @@ static int loglik_dense(int family, const char* entry, const double* X, const do
     ea.P = P;
     ea.intercept = fit_intercept ? 1 : 0;
     ea.nbeta = n_beta;
-    ea.slot_bytes = eval_slot_bytes(p, eta_offset != nullptr);
+    ea.row_weight = row_weight;
+    if (row_weight) ea.w_last4 = (uintptr_t)(row_weight + n_total) - 4;
+    ea.slot_bytes = eval_slot_bytes(p, (eta_offset ? 1 : 0) + (row_weight ? 1 : 0));
     const int PM = ((P + 7) / 8) * 8;
     const int budget = 160 * 1024 - (n_beta * PM + 2 * PM + 64) * 8;
     ea.nslot = std::max(2, std::min(budget / ea.slot_bytes, 6));
-    DLSA_HIP_TRY(launch_loglik_eval(ea, family, pl.n_chunks, stream));
+    if (row_weight)
+      DLSA_HIP_TRY(launch_loglik_eval_wgt(ea, family, pl.n_chunks, stream));
+    else
+      DLSA_HIP_TRY(launch_loglik_eval(ea, family, pl.n_chunks, stream));
   }
   DLSA_HIP_TRY(launch_loglik_reduce(d_partial, d_pcb, K, n_beta, loglik, stream));
   if (loglik_sum) DLSA_HIP_TRY(launch_loglik_total(loglik, K, n_beta, loglik_sum, stream));
@@ -306,6 +340,29 @@ int dlsa_poisson_loglik_batched_sum_offset(const double* X, const double* y,
   return loglik_dense(FAMILY_POISSON, "dlsa_poisson_loglik_batched_sum", X, y, offsets, K, p,
                       fit_intercept, center, scale, betas,
                       n_beta, loglik, loglik_sum, stream, eta_offset);
+}
+
+int dlsa_logistic_loglik_batched_sum_weighted(const double* X, const double* y,
+                                              const double* row_weight, const int64_t* offsets,
+                                              int32_t K, int32_t p, int32_t fit_intercept,
+                                              const double* center, const double* scale,
+                                              const double* betas, int32_t n_beta, double* loglik,
+                                              double* loglik_sum, void* stream) {
+  return loglik_dense(FAMILY_LOGISTIC, "dlsa_logistic_loglik_batched_sum_weighted", X, y, offsets,
+                      K, p, fit_intercept, center, scale, betas, n_beta, loglik, loglik_sum,
+                      stream, nullptr, row_weight);
+}
+
+int dlsa_poisson_loglik_batched_sum_weighted(const double* X, const double* y,
+                                             const double* eta_offset, const double* row_weight,
+                                             const int64_t* offsets, int32_t K, int32_t p,
+                                             int32_t fit_intercept, const double* center,
+                                             const double* scale, const double* betas,
+                                             int32_t n_beta, double* loglik, double* loglik_sum,
+                                             void* stream) {
+  return loglik_dense(FAMILY_POISSON, "dlsa_poisson_loglik_batched_sum_weighted", X, y, offsets, K,
+                      p, fit_intercept, center, scale, betas, n_beta, loglik, loglik_sum, stream,
+                      eta_offset, row_weight);
 }
 
 int dlsa_logistic_loglik_categorical(const double* Xn, const uint8_t* codes, const double* y,

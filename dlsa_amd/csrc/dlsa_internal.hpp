@@ -49,13 +49,16 @@ struct FamilyRules {
   bool sums_ll_const;
   // starts from a device-computed point (launch_poisson_start), which may end partitions
   bool device_start;
-  // may carry a per-row eta_offset (the OFS kernels, PassArgsOfs)
+  // may carry a per-row eta_offset (the EX_OFS kernels, PassArgsOfs)
   bool offset;
+  // may carry per-row prior weights (the EX_WGT kernels, PassArgsWgt): fused
+  // path only, exact passes on the fp64 MFMA
+  bool weights;
   int max_p;  // largest P = p + intercept
 };
-constexpr FamilyRules kLogisticRules = {true, true, false, false, false, DLSA_MAX_P};
-constexpr FamilyRules kGaussianRules = {false, false, false, false, false, DLSA_MAX_P};
-constexpr FamilyRules kPoissonRules = {true, false, true, true, true, DLSA_MAX_P_FUSED};
+constexpr FamilyRules kLogisticRules = {true, true, false, false, false, true, DLSA_MAX_P};
+constexpr FamilyRules kGaussianRules = {false, false, false, false, false, false, DLSA_MAX_P};
+constexpr FamilyRules kPoissonRules = {true, false, true, true, true, true, DLSA_MAX_P_FUSED};
 constexpr FamilyRules family_rules(int family) {
   return family == FAMILY_GAUSSIAN ? kGaussianRules
          : family == FAMILY_POISSON ? kPoissonRules
@@ -82,20 +85,27 @@ inline hipError_t unit_dispatch(IntList<FAMS...>, IntList<NTS...>, int family, i
   (void)((family == FAMS && (by_nt(std::integral_constant<int, FAMS>{}), true)) || ...);
   return e;
 }
+// Row extras: the per-row 8-byte streams a pass reads beside X and y, a
+// compile-time mask of its kernels.  Each extra streams like y: a
+// bounds-checked buffer resource of its own over the chunk, one more LDS-DMA
+// load of 256 B per 32-row block, placed behind y in the ring slot in bit
+// order (the offset, then the weight).
+enum : int { EX_NONE = 0, EX_OFS = 1, EX_WGT = 2 };
+constexpr int ex_count(int ex) { return (ex & 1) + ((ex >> 1) & 1); }
 // Row of a pass's routing table: the unit entry point that holds the
-// instantiations of these families, with / without the offset, for NT in
+// instantiations of these families and this row-extras mask for NT in
 // [nt_lo, nt_hi]
 template <typename Fn>
 struct UnitRow {
   unsigned families;  // IntList::mask
-  bool ofs;
+  int extras;         // EX_* mask
   int nt_lo, nt_hi;
   Fn* launch;
 };
 template <typename Fn, size_t N>
-inline Fn* find_unit(const UnitRow<Fn> (&table)[N], int family, bool ofs, int NT) {
+inline Fn* find_unit(const UnitRow<Fn> (&table)[N], int family, int extras, int NT) {
   for (const UnitRow<Fn>& r : table)
-    if (((r.families >> family) & 1u) && r.ofs == ofs && NT >= r.nt_lo && NT <= r.nt_hi)
+    if (((r.families >> family) & 1u) && r.extras == extras && NT >= r.nt_lo && NT <= r.nt_hi)
       return r.launch;
   return nullptr;
 }
@@ -173,14 +183,31 @@ struct PassArgsOfs : PassArgs {
   const double* eta_offset;  // [n_total] or null (none)
   uintptr_t o_last4;         // last 4-B address inside eta_offset
 };
-template <bool OFS>
+// ... and with per-row prior weights omega (EX_WGT): IRLS weight omega w,
+// score residual omega (y - mu), log-likelihood terms omega l_i.  Only the
+// weighted instantiations take this struct, for the same reason; PassArgs
+// and PassArgsOfs keep their size.  It is what the dispatchers are handed
+// (every other kernel takes its slice).
+struct PassArgsWgt : PassArgsOfs {
+  const double* row_weight;  // [n_total] or null (none)
+  uintptr_t w_last4;         // last 4-B address inside row_weight
+};
+template <int EX>
 struct pass_args_of {
+  typedef PassArgsWgt type;
+};
+template <>
+struct pass_args_of<EX_NONE> {
   typedef PassArgs type;
 };
 template <>
-struct pass_args_of<true> {
+struct pass_args_of<EX_OFS> {
   typedef PassArgsOfs type;
 };
+// the row-extras mask the dispatchers route on
+inline int pass_extras(const PassArgsWgt& a) {
+  return (a.eta_offset ? EX_OFS : 0) | (a.row_weight ? EX_WGT : 0);
+}
 
 // A/B knobs of profiling builds.  The product library reads no environment
 // variable that changes a result (include/dlsa_hip.h): env_knob() is getenv
@@ -360,6 +387,16 @@ struct EvalArgs {
   const double* eta_offset;
   uintptr_t o_last4;
 };
+// EvalArgs of the weighted instantiations (eval_pass_wgt.hip): every row's
+// terms are multiplied by row_weight.  The unweighted kernels keep EvalArgs.
+struct EvalArgsWgt : EvalArgs {
+  const double* row_weight;  // [n_total]
+  uintptr_t w_last4;
+};
+template <int EX>
+struct eval_args_of {
+  typedef typename std::conditional<(EX & EX_WGT) != 0, EvalArgsWgt, EvalArgs>::type type;
+};
 
 // Wide-P path (DLSA_MAX_P_FUSED < P <= DLSA_MAX_P, wide_exact.hip): a row
 // pass (eta, weights, gradient, log-lik) and a separate Gram pass over
@@ -522,9 +559,11 @@ int wide_newton_lds_bytes(int NB);
 hipError_t launch_loglik_eval(const EvalArgs& a, int family, int n_chunks, hipStream_t s);
 hipError_t launch_loglik_reduce(const double* partial, const int32_t* pcb, int K, int B,
                                 double* out, hipStream_t s);
-int eval_slot_bytes(int p, bool eta_offset = false);  // + the offset's 256 B behind y
+// weighted evaluation (eval_pass_wgt.hip); a.row_weight must be set
+hipError_t launch_loglik_eval_wgt(const EvalArgsWgt& a, int family, int n_chunks, hipStream_t s);
+int eval_slot_bytes(int p, int n_extras = 0);  // + 256 B per row extra behind y
 // per-wave fp64 pass (irls_wave_impl.hpp): P <= 128
-hipError_t launch_irls_wave(const PassArgsOfs& a, int NT, bool standardize, int family,
+hipError_t launch_irls_wave(const PassArgsWgt& a, int NT, bool standardize, int family,
                             int n_chunks, hipStream_t s);
 int wave_lds_bytes(int NT, int p);
 constexpr int kWaveMaxNT = 8;
@@ -540,9 +579,9 @@ constexpr int kOzMaxNT = 7;
 bool ols_stream_applies(int NT);
 hipError_t launch_ols_stream(const PassArgs& a, int NT, bool standardize, int n_chunks,
                              hipStream_t s);
-hipError_t launch_irls_coop(const PassArgsOfs& a, int NT, int prec, bool standardize, int family,
+hipError_t launch_irls_coop(const PassArgsWgt& a, int NT, int prec, bool standardize, int family,
                             int n_chunks, hipStream_t s);
-int coop_slot_bytes(int NT, int p, bool eta_offset = false);  // + the offset's 256 B behind y
+int coop_slot_bytes(int NT, int p, int n_extras = 0);  // + 256 B per row extra behind y
 int coop_extra_bytes(int NT);  // LDS beyond the ring
 hipError_t launch_newton_solve(const SolveArgs& a, int K, hipStream_t s);
 hipError_t launch_fit_init(const int64_t* offsets_dev, int K, int P, int start_phase,
@@ -562,6 +601,20 @@ hipError_t launch_poisson_start(const double* y, const int64_t* offsets_dev, int
                                 int intercept, double* theta, double* theta0, int32_t* phase,
                                 int32_t* status, hipStream_t s,
                                 const double* eta_offset = nullptr);
+// Pre-pass of a weighted fit (aux_kernels.hip), after fit_init: one fixed-order
+// pass per partition over the prior weights omega.  A negative or non-finite
+// omega ends the partition NONFINITE, sum omega = 0 SINGULAR (phase
+// PHASE_DONE, outputs left zeroed by fit_init); nothing per row is stored.
+// Logistic: statuses only, the start stays theta = 0
+hipError_t launch_weight_check(const double* row_weight, const int64_t* offsets_dev, int K,
+                               int32_t* phase, int32_t* status, hipStream_t s);
+// Poisson: the weighted start point, theta0[k] = log(sum omega y / sum omega
+// exp(o)) with an intercept (o = 0 without an offset); the checks of
+// launch_poisson_start too, and sum omega y = 0 ends the partition SINGULAR
+hipError_t launch_poisson_start_wgt(const double* y, const double* eta_offset,
+                                    const double* row_weight, const int64_t* offsets_dev, int K,
+                                    int P, int intercept, double* theta, double* theta0,
+                                    int32_t* phase, int32_t* status, hipStream_t s);
 hipError_t launch_polish_mark(int K, int32_t* phase, const int32_t* status, int32_t* counters,
                               hipStream_t s);
 // theta_rec[k] = theta[k] for the partitions in phase `ph` (before a pass

@@ -286,6 +286,9 @@ struct DenseFit {
   FitStart start;
   // FAMILY_POISSON: per-row offset of eta [n_total], device, or null (fused path only)
   const double* eta_offset = nullptr;
+  // per-row prior weights omega [n_total], device, or null (logistic and
+  // Poisson, fused path only)
+  const double* row_weight = nullptr;
 };
 int fit_fused(const DenseFit& f);  // P <= DLSA_MAX_P_FUSED (fit_fused.hip)
 int fit_wide(const DenseFit& f);   // P > DLSA_MAX_P_FUSED (fit_wide.hip)

@@ -22,7 +22,7 @@ struct FusedFit {
   StreamTimer timed;
   Readback h;
   int32_t* h_route = nullptr;  // [K] phases with stale partitions marked (one launch)
-  PassArgsOfs pa;  // (eta_offset null unless the fit has a per-row offset)
+  PassArgsWgt pa;  // (eta_offset / row_weight null unless the fit has that row extra)
   SolveArgs sa;
   int approx_prec = PREC_BF16;
   bool standardize = false;
@@ -84,8 +84,10 @@ void FusedFit::set_pass_args(const Plan& pl, const Workspace& ws, const Layout& 
     pa.x_last16 = ((xend + 15) & ~(uintptr_t)15) - 16;
     pa.y_last4 = (uintptr_t)(f.y + n_total) - 4;
     if (f.eta_offset) pa.o_last4 = (uintptr_t)(f.eta_offset + n_total) - 4;
+    if (f.row_weight) pa.w_last4 = (uintptr_t)(f.row_weight + n_total) - 4;
   }
   pa.eta_offset = f.eta_offset;
+  pa.row_weight = f.row_weight;
   pa.p = f.p;
   pa.P = P;
   pa.intercept = f.fit_intercept ? 1 : 0;
@@ -94,7 +96,7 @@ void FusedFit::set_pass_args(const Plan& pl, const Workspace& ws, const Layout& 
   // row phase and barrier waits overlap the other's tile phase (measured
   // 27.4 -> 21.8 ms per bf16 pass at config 2 against one workgroup with a
   // deeper ring)
-  pa.slot_bytes = coop_slot_bytes(pl.NT, f.p, f.eta_offset != nullptr);
+  pa.slot_bytes = coop_slot_bytes(pl.NT, f.p, ex_count(pass_extras(pa)));
   const int wg_per_cu = pl.NT < 8 ? 2 : 1;
   const int budget = 160 * 1024 / wg_per_cu - coop_extra_bytes(pl.NT);
   pa.nslot = std::max(2, std::min(budget / pa.slot_bytes, 6));
@@ -138,14 +140,14 @@ hipError_t FusedFit::pass(int ph, const Plan& q, bool full, const std::vector<in
     if (e != hipSuccess) return e;
   }
   hipError_t e = timed(f64 ? &g_stats.ms_pass_fp64 : &g_stats.ms_pass_fp32, [&] {
-    PassArgsOfs pc = pa;
+    PassArgsWgt pc = pa;
     pc.colmax = (oz || rec_x) ? d_colmax : nullptr;
     pc.zcolmax = (oz || rec_z) ? d_zcolmax : nullptr;
     pc.theta_rec = d_threc;
     if (oz) {
       hipError_t eo = launch_irls_oz(pc, q.NT, standardize, family, q.n_chunks, stream);
       if (eo != hipSuccess || !split) return eo;
-      PassArgsOfs ps = pa;  // the stale partitions on the fp64 MFMA
+      PassArgsWgt ps = pa;  // the stale partitions on the fp64 MFMA
       ps.want_phase = PHASE_F64_STALE;
       return launch_irls_wave(ps, q.NT, standardize, family, q.n_chunks, stream);
     }
@@ -196,7 +198,7 @@ hipError_t FusedFit::spec_pass(const Plan& q, bool full) {
     if (e != hipSuccess) return e;
   }
   return timed(&g_stats.ms_pass_fp32, [&] {
-    PassArgsOfs pc = pa;
+    PassArgsWgt pc = pa;
     pc.colmax = nullptr;
     pc.zcolmax = zg ? d_zcolmax : nullptr;
     pc.theta_rec = d_threc;
@@ -270,10 +272,19 @@ int FusedFit::run() {
   const int start_phase =
       (opt.hessian_mode == DLSA_HESSIAN_FP64 || !rules.iterates) ? PHASE_F64 : PHASE_F32;
   DLSA_HIP_TRY(fit_init(sa, d_offsets, K, start_phase, stream));
-  if (rules.device_start)  // Poisson: the start point; ends the partitions that have no MLE
+  if (rules.device_start && f.row_weight)  // Poisson, weighted: start point and weight check
+    DLSA_HIP_TRY(launch_poisson_start_wgt(f.y, f.eta_offset, f.row_weight, d_offsets, K, P,
+                                          f.fit_intercept ? 1 : 0, sa.theta,
+                                          const_cast<double*>(sa.theta0), sa.phase, sa.status,
+                                          stream));
+  else if (rules.device_start)  // Poisson: the start point; ends the partitions that have no MLE
     DLSA_HIP_TRY(launch_poisson_start(f.y, d_offsets, K, P, f.fit_intercept ? 1 : 0, sa.theta,
                                       const_cast<double*>(sa.theta0), sa.phase, sa.status, stream,
                                       f.eta_offset));
+  else if (f.row_weight)  // logistic, weighted: the weight check (statuses only)
+    DLSA_HIP_TRY(launch_weight_check(f.row_weight, d_offsets, K, sa.phase, sa.status, stream));
+  // the pre-pass may have ended partitions
+  const bool pre_pass = rules.device_start || f.row_weight != nullptr;
   int n_running[kRunPhases] = {0, 0, 0};
   for (int k = 0; k < K; ++k)
     if (offsets[k + 1] > offsets[k]) n_running[start_phase]++;
@@ -282,8 +293,9 @@ int FusedFit::run() {
   h_route = h.phase + K;
   const bool trace = trace_enabled();
 
-  // (Poisson weights are unbounded: no int8 exact pass, DLSA_EXACT_AUTO is fp64 MFMA)
-  use_oz = rules.digit_scales && opt.exact_pass != DLSA_EXACT_FP64 &&
+  // (Poisson weights are unbounded: no int8 exact pass, DLSA_EXACT_AUTO is fp64 MFMA;
+  // so are prior weights: the digit-grid fallback bound relies on sqrt(w) <= 1/2)
+  use_oz = rules.digit_scales && !f.row_weight && opt.exact_pass != DLSA_EXACT_FP64 &&
            approx_prec == PREC_BF16 && oz_applies(pl.NT, f.p) && pl.max_chunk_rows <= kOzMaxRows;
   d_colmax = (uint32_t*)ws.at(L.off_colmax);
   d_zcolmax = (uint32_t*)ws.at(L.off_zcolmax);
@@ -307,7 +319,7 @@ int FusedFit::run() {
       DLSA_HIP_TRY(reenter_level(sa, K, start_phase, h, n_running, stream));
     else
       DLSA_HIP_TRY(read_phases(sa, K, h, stream));
-    if (lvl == 0 && rules.device_start) {  // less the partitions the start point ended
+    if (lvl == 0 && pre_pass) {  // less the partitions the start point / weight check ended
       n_running[start_phase] = 0;
       for (int k = 0; k < K; ++k)
         if (h.phase[k] == start_phase) n_running[start_phase]++;

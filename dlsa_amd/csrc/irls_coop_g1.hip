@@ -3,6 +3,6 @@
 
 namespace dlsa {
 
-DLSA_COOP_UNIT(launch_irls_coop_g1, FamLogisticGaussian, false, 1, 2, 3, 4)
+DLSA_COOP_UNIT(launch_irls_coop_g1, FamLogisticGaussian, EX_NONE, 1, 2, 3, 4)
 
 }  // namespace dlsa

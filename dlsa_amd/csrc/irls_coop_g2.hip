@@ -3,6 +3,6 @@
 
 namespace dlsa {
 
-DLSA_COOP_UNIT(launch_irls_coop_g2, FamLogisticGaussian, false, 5, 6)
+DLSA_COOP_UNIT(launch_irls_coop_g2, FamLogisticGaussian, EX_NONE, 5, 6)
 
 }  // namespace dlsa

@@ -3,6 +3,6 @@
 
 namespace dlsa {
 
-DLSA_COOP_UNIT(launch_irls_coop_g3, FamLogisticGaussian, false, 7)
+DLSA_COOP_UNIT(launch_irls_coop_g3, FamLogisticGaussian, EX_NONE, 7)
 
 }  // namespace dlsa

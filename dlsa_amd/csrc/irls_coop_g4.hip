@@ -3,6 +3,6 @@
 
 namespace dlsa {
 
-DLSA_COOP_UNIT(launch_irls_coop_g4, FamLogisticGaussian, false, 8)
+DLSA_COOP_UNIT(launch_irls_coop_g4, FamLogisticGaussian, EX_NONE, 8)
 
 }  // namespace dlsa

@@ -3,6 +3,6 @@
 
 namespace dlsa {
 
-DLSA_COOP_UNIT(launch_irls_coop_g5, FamLogisticGaussian, false, 9, 10)
+DLSA_COOP_UNIT(launch_irls_coop_g5, FamLogisticGaussian, EX_NONE, 9, 10)
 
 }  // namespace dlsa

@@ -3,6 +3,6 @@
 
 namespace dlsa {
 
-DLSA_COOP_UNIT(launch_irls_coop_g6, FamLogisticGaussian, false, 11, 12)
+DLSA_COOP_UNIT(launch_irls_coop_g6, FamLogisticGaussian, EX_NONE, 11, 12)
 
 }  // namespace dlsa

@@ -134,18 +134,32 @@ constexpr int coop_waves(int NT) { return NT > 8 ? 8 : 4; }
 // A slot holds exactly the block's pieces: a wave's surplus issues (the piece
 // count is rounded up to the wave count so that every wave waits on the same
 // vmcnt) re-load the last piece onto itself.
-// With a per-row offset (Poisson, OFS) its RB doubles follow y.
-inline int coop_slot_bytes_impl(int NT, int p, bool eta_offset = false) {
-  return 16 + npieces_for(p) * 1024 + 16 * NT * 8 + RB * 8 + (eta_offset ? RB * 8 : 0);
+// Each row extra (the Poisson offset, the prior weights: EX_*) adds its RB
+// doubles behind y.  (constexpr for coop_ring_fits below, so npieces_for(p)
+// is spelled out)
+constexpr int coop_slot_bytes_impl(int NT, int p, int n_extras = 0) {
+  return 16 + ((RB * p * 8 + 16 + 1023) / 1024) * 1024 + 16 * NT * 8 + RB * 8 + n_extras * RB * 8;
 }
 
 // LDS beyond the ring: w, r of the block [2][RB] fp64, center / 1/scale
 // [2][PMAX] fp64, and the bf16 MFMA operand image of the block z = sqrt(w) x,
 // [PMAX][RB + 16] bf16 (feature-major, so one lane's 8 consecutive k are one
 // 16-byte read).
-inline int coop_extra_bytes_impl(int NT) {
+constexpr int coop_extra_bytes_impl(int NT) {
   return (2 * RB + 2 * 16 * NT) * 8 + 16 * NT * (RB + 16) * 2;
 }
+
+// The smallest ring (nslot = 2) of the widest slot of every NT, with both row
+// extras, fits the LDS share of a workgroup (set_pass_args, fit_fused.hip:
+// two workgroups per CU below NT = 8).
+constexpr bool coop_ring_fits(int n_extras) {
+  for (int NT = 1; NT <= 12; ++NT)
+    if (2 * coop_slot_bytes_impl(NT, 16 * NT, n_extras) + coop_extra_bytes_impl(NT) >
+        160 * 1024 / (NT < 8 ? 2 : 1))
+      return false;
+  return true;
+}
+static_assert(coop_ring_fits(2), "a two-slot ring with the offset and the weight fits the LDS");
 
 // Tile phase of wave WID for one 32-row block.
 template <int NT, int W, int PREC, bool STD, int WID, typename Acc>
@@ -219,18 +233,28 @@ __device__ __forceinline__ void store_tiles(Acc (&acc)[(CG<NT, W>::TPW)], double
 // value of the bf16 image) into a.zcolmax (2: the bf16 passes of partitions
 // near convergence); the Ozaki exact pass takes its digit scales from the
 // last records (irls_oz_impl.hpp)
-// OFS (FAMILY_POISSON only): eta = x . theta + a.eta_offset[row]; the offset
-// streams like y, one more DMA piece of RB * 8 bytes per block behind y
-template <int NT, int W, int PREC, bool STD, int FAM, int CM = 0, bool OFS = false>
+// EX (row extras, EX_* mask): each streams like y, one more DMA piece of
+// RB * 8 bytes per block behind y, the offset first.
+//   EX_OFS (FAMILY_POISSON only): eta = x . theta + a.eta_offset[row]
+//   EX_WGT: prior weights omega = a.row_weight[row]: w, r and the row's
+//   log-likelihood terms are multiplied by omega once, after mu (so the bf16 /
+//   fp32 images are sqrt(omega w) x); CM = 0 only
+template <int NT, int W, int PREC, bool STD, int FAM, int CM = 0, int EX = EX_NONE>
 __global__ __launch_bounds__(64 * W, (W == 8 || NT < 8) ? 2 : 1)
-void irls_coop_kernel(const typename pass_args_of<OFS>::type a) {
+void irls_coop_kernel(const typename pass_args_of<EX>::type a) {
   using G = CG<NT, W>;
   using Acc = typename std::conditional<PREC == PREC_F64, d4, f4>::type;
   constexpr int RPW = G::RPW, LPR = G::LPR;
   constexpr int M = G::M;
+  constexpr bool OFS = (EX & EX_OFS) != 0, WGT = (EX & EX_WGT) != 0;
   static_assert(!OFS || FAM == FAMILY_POISSON, "the offset is the Poisson family's");
-  constexpr int NLD = 1 + (OFS ? 1 : 0);          // loads per block beside X: y (and the offset)
+  static_assert(!WGT || CM == 0, "no digit-scale records of a weighted pass");
+  constexpr int NLD = 1 + ex_count(EX);       // loads per block beside X: y and the row extras
   constexpr int MAXW = 4 * (G::MAX_D + NLD);  // nslot <= 6
+  // a wave has at most nslot - 1 <= 5 blocks of d + NLD <= MAX_D + NLD loads
+  // outstanding: within the 6-bit vmcnt (5 (9 + 3) = 60 at NT = 8 with both extras)
+  static_assert(5 * (G::MAX_D + NLD) <= 63, "outstanding loads exceed the vmcnt counter");
+  constexpr int WOFF = RB * (1 + (OFS ? 1 : 0));  // doubles from y to the weights in a slot
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int chunk = blockIdx.x;
@@ -329,6 +353,11 @@ void irls_coop_kernel(const typename pass_args_of<OFS>::type a) {
     const uintptr_t ocb = (uintptr_t)(a.eta_offset + row0);
     or_rsrc = uniform_rsrc(ocb, a.o_last4 + 4 - ocb);
   }
+  [[maybe_unused]] __amdgpu_buffer_rsrc_t wr_rsrc;
+  if constexpr (WGT) {
+    const uintptr_t wcb = (uintptr_t)(a.row_weight + row0);
+    wr_rsrc = uniform_rsrc(wcb, a.w_last4 + 4 - wcb);
+  }
   auto issue = [&](int blk) {
     const int bb = blk < nb ? blk : nb - 1;  // tail: harmless re-fetch, fixed counts
     char* sbase = smem + (blk % nslot) * slot_bytes;
@@ -346,6 +375,9 @@ void irls_coop_kernel(const typename pass_args_of<OFS>::type a) {
     if constexpr (OFS)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(or_rsrc, (lds_void_t*)(sbase + slot_x + RB * 8), 4,
                                                vy, bb * RB * 8, 0, 0);
+    if constexpr (WGT)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(wr_rsrc, (lds_void_t*)(sbase + slot_x + WOFF * 8),
+                                               4, vy, bb * RB * 8, 0, 0);
   };
 
   // every wave issues d + NLD loads per block, in block order: with at most
@@ -404,6 +436,10 @@ void irls_coop_kernel(const typename pass_args_of<OFS>::type a) {
       // selects on `valid` below keep it out of w, r and the log-likelihood
       if constexpr (OFS) e += ys[RB + rB];
       const double yv = ys[rB];
+      // the prior weight, selected on `valid`: a padded row's is the next
+      // partition's (possibly NaN) and reaches nothing
+      [[maybe_unused]] double om = 1.0;
+      if constexpr (WGT) om = valid ? ys[WOFF + rB] : 0.0;
       double w, r;
       if constexpr (FAM == FAMILY_LOGISTIC && DLSA_ABLATE == 2) {
         w = 0.25;
@@ -419,7 +455,10 @@ void irls_coop_kernel(const typename pass_args_of<OFS>::type a) {
           // exact fp64 in the fp64 pass (its value is returned); fp32 log in
           // the approximate passes, where it only drives step halving
           const double sp = (PREC == PREC_F64) ? log1p(ea) : (double)__logf(1.0f + (float)ea);
-          llacc += yv * e - (fmax(e, 0.0) + sp);
+          if constexpr (WGT)
+            llacc += om * (yv * e - (fmax(e, 0.0) + sp));
+          else
+            llacc += yv * e - (fmax(e, 0.0) + sp);
         }
       } else if constexpr (FAM == FAMILY_POISSON) {
         // log link: mu = w = exp(eta).  A padded row's eta is never
@@ -431,14 +470,26 @@ void irls_coop_kernel(const typename pass_args_of<OFS>::type a) {
         w = mu;
         r = yv - mu;
         if (valid && sl == 0) {
-          llacc += yv * e - mu;
-          if constexpr (PREC == PREC_F64)
-            if (yv != 0.0 && yv != 1.0) llcacc -= lgamma1p(yv);  // 0 at y = 0, 1
+          if constexpr (WGT)
+            llacc += om * (yv * e - mu);
+          else
+            llacc += yv * e - mu;
+          if constexpr (PREC == PREC_F64) {
+            if constexpr (WGT) {
+              if (yv != 0.0 && yv != 1.0) llcacc -= om * lgamma1p(yv);
+            } else {
+              if (yv != 0.0 && yv != 1.0) llcacc -= lgamma1p(yv);  // 0 at y = 0, 1
+            }
+          }
         }
       } else {  // gaussian (OLS): mu = eta, w = 1, ll = -rss/2
         w = 1.0;
         r = yv - e;
         if (valid && sl == 0) llacc -= 0.5 * r * r;
+      }
+      if constexpr (WGT) {  // once, after mu; ahead of the padded rows' zeroing
+        w *= om;
+        r *= om;
       }
       if (!valid) {
         w = 0.0;
@@ -580,10 +631,10 @@ void irls_coop_kernel(const typename pass_args_of<OFS>::type a) {
   }
 }
 
-template <int NT, int W, int PREC, bool STD, int FAM, int CM = 0, bool OFS = false>
-static hipError_t launch_c(const typename pass_args_of<OFS>::type& a, int n_chunks,
+template <int NT, int W, int PREC, bool STD, int FAM, int CM = 0, int EX = EX_NONE>
+static hipError_t launch_c(const typename pass_args_of<EX>::type& a, int n_chunks,
                            hipStream_t s) {
-  auto kern = irls_coop_kernel<NT, W, PREC, STD, FAM, CM, OFS>;
+  auto kern = irls_coop_kernel<NT, W, PREC, STD, FAM, CM, EX>;
   const size_t lds =
       (size_t)a.nslot * a.slot_bytes + coop_extra_bytes_impl(NT);
   hipError_t e = ensure_max_lds((const void*)kern, 160 * 1024);
@@ -595,31 +646,34 @@ static hipError_t launch_c(const typename pass_args_of<OFS>::type& a, int n_chun
 template <int V>
 using int_c = std::integral_constant<int, V>;
 
-// The launcher of one (NT, family, offset): the precision, CM and
+// The launcher of one (NT, family, row extras): the precision, CM and
 // standardisation selection, each arm guarded by the family's rules, so a
 // unit instantiates the kernels its families may launch and no other (no CM
-// kernel without digit scales or above kOzMaxNT, one precision for a family
-// that does not iterate, OFS only with an offset).  A kernel without an
-// offset takes the PassArgs slice of `a`.
-template <int NT, int FAM, bool OFS>
-static hipError_t launch_coop_nt(const PassArgsOfs& a, int prec, bool std_, int n_chunks,
+// kernel without digit scales, above kOzMaxNT or with weights, one precision
+// for a family that does not iterate, an extra only with its array).  A
+// kernel takes the slice of `a` its extras need.
+template <int NT, int FAM, int EX>
+static hipError_t launch_coop_nt(const PassArgsWgt& a, int prec, bool std_, int n_chunks,
                                  hipStream_t s) {
   constexpr FamilyRules R = family_rules(FAM);
   constexpr int W = coop_waves(NT);
+  constexpr bool OFS = (EX & EX_OFS) != 0, WGT = (EX & EX_WGT) != 0;
   static_assert(!OFS || R.offset, "an offset kernel of a family without one");
+  static_assert(!WGT || R.weights, "a weighted kernel of a family without weights");
   if (!R.iterates && prec != PREC_F64) return hipErrorInvalidValue;
-  if (!R.digit_scales && (a.colmax || a.zcolmax)) return hipErrorInvalidValue;
+  if ((!R.digit_scales || WGT) && (a.colmax || a.zcolmax)) return hipErrorInvalidValue;
   if (R.sums_ll_const && prec == PREC_F64 && !a.slab_llc) return hipErrorInvalidValue;
   if (OFS && !a.eta_offset) return hipErrorInvalidValue;
-  const typename pass_args_of<OFS>::type& ka = a;
+  if (WGT && !a.row_weight) return hipErrorInvalidValue;
+  const typename pass_args_of<EX>::type& ka = a;
   auto go = [&](auto prec_c, auto cm_c) {
     constexpr int PREC = decltype(prec_c)::value, CM = decltype(cm_c)::value;
-    return std_ ? launch_c<NT, W, PREC, true, FAM, CM, OFS>(ka, n_chunks, s)
-                : launch_c<NT, W, PREC, false, FAM, CM, OFS>(ka, n_chunks, s);
+    return std_ ? launch_c<NT, W, PREC, true, FAM, CM, EX>(ka, n_chunks, s)
+                : launch_c<NT, W, PREC, false, FAM, CM, EX>(ka, n_chunks, s);
   };
   if constexpr (R.iterates) {
     if (prec == PREC_BF16) {
-      if constexpr (R.digit_scales && NT <= kOzMaxNT) {
+      if constexpr (R.digit_scales && NT <= kOzMaxNT && !WGT) {
         switch ((a.colmax ? 1 : 0) | (a.zcolmax ? 2 : 0)) {
           case 1: return go(int_c<PREC_BF16>{}, int_c<1>{});
           case 2: return go(int_c<PREC_BF16>{}, int_c<2>{});
@@ -634,16 +688,16 @@ static hipError_t launch_coop_nt(const PassArgsOfs& a, int prec, bool std_, int 
 }
 
 // Entry point of a compilation unit, one line per unit:
-//   DLSA_COOP_UNIT(name, family set (an IntList), OFS, NT...)
+//   DLSA_COOP_UNIT(name, family set (an IntList), row extras (EX_* mask), NT...)
 // irls_coop.hip lists the units and routes to them.
-typedef hipError_t CoopUnitFn(const PassArgsOfs& a, int NT, int prec, bool std_, int family,
+typedef hipError_t CoopUnitFn(const PassArgsWgt& a, int NT, int prec, bool std_, int family,
                               int n_chunks, hipStream_t s);
-#define DLSA_COOP_UNIT(name, FAMS, OFS, ...)                                                 \
-  hipError_t name(const PassArgsOfs& a, int NT, int prec, bool std_, int family, int n_chunks, \
+#define DLSA_COOP_UNIT(name, FAMS, EX, ...)                                                  \
+  hipError_t name(const PassArgsWgt& a, int NT, int prec, bool std_, int family, int n_chunks, \
                   hipStream_t s) {                                                           \
     return unit_dispatch(FAMS{}, IntList<__VA_ARGS__>{}, family, NT, [&](auto fam, auto nt) { \
-      return launch_coop_nt<decltype(nt)::value, decltype(fam)::value, OFS>(a, prec, std_,   \
-                                                                            n_chunks, s);    \
+      return launch_coop_nt<decltype(nt)::value, decltype(fam)::value, (EX)>(a, prec, std_,  \
+                                                                             n_chunks, s);   \
     });                                                                                      \
   }
 

@@ -3,6 +3,6 @@
 
 namespace dlsa {
 
-DLSA_COOP_UNIT(launch_irls_coop_pois_g1, FamPoisson, false, 1, 2, 3, 4)
+DLSA_COOP_UNIT(launch_irls_coop_pois_g1, FamPoisson, EX_NONE, 1, 2, 3, 4)
 
 }  // namespace dlsa

@@ -3,6 +3,6 @@
 
 namespace dlsa {
 
-DLSA_COOP_UNIT(launch_irls_coop_pois_g2, FamPoisson, false, 5, 6, 7, 8)
+DLSA_COOP_UNIT(launch_irls_coop_pois_g2, FamPoisson, EX_NONE, 5, 6, 7, 8)
 
 }  // namespace dlsa

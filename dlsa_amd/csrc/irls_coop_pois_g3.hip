@@ -3,6 +3,6 @@
 
 namespace dlsa {
 
-DLSA_COOP_UNIT(launch_irls_coop_pois_g3, FamPoisson, false, 9, 10, 11, 12)
+DLSA_COOP_UNIT(launch_irls_coop_pois_g3, FamPoisson, EX_NONE, 9, 10, 11, 12)
 
 }  // namespace dlsa

@@ -4,6 +4,6 @@
 
 namespace dlsa {
 
-DLSA_COOP_UNIT(launch_irls_coop_pois_ofs_g1, FamPoisson, true, 1, 2, 3, 4)
+DLSA_COOP_UNIT(launch_irls_coop_pois_ofs_g1, FamPoisson, EX_OFS, 1, 2, 3, 4)
 
 }  // namespace dlsa

@@ -4,6 +4,6 @@
 
 namespace dlsa {
 
-DLSA_COOP_UNIT(launch_irls_coop_pois_ofs_g2, FamPoisson, true, 5, 6, 7, 8)
+DLSA_COOP_UNIT(launch_irls_coop_pois_ofs_g2, FamPoisson, EX_OFS, 5, 6, 7, 8)
 
 }  // namespace dlsa

@@ -4,6 +4,6 @@
 
 namespace dlsa {
 
-DLSA_COOP_UNIT(launch_irls_coop_pois_ofs_g3, FamPoisson, true, 9, 10, 11, 12)
+DLSA_COOP_UNIT(launch_irls_coop_pois_ofs_g3, FamPoisson, EX_OFS, 9, 10, 11, 12)
 
 }  // namespace dlsa

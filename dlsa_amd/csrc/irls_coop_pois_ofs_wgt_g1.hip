@@ -1,0 +1,9 @@
+// Poisson instantiations of the cooperative pass with a per-row offset and
+// per-row prior weights (eta = x . theta + eta_offset, IRLS weight omega w) for NT in {1, 2, 3, 4}.
+#include "irls_coop_impl.hpp"
+
+namespace dlsa {
+
+DLSA_COOP_UNIT(launch_irls_coop_pois_ofs_wgt_g1, FamPoisson, EX_OFS | EX_WGT, 1, 2, 3, 4)
+
+}  // namespace dlsa

@@ -1,0 +1,9 @@
+// Poisson instantiations of the cooperative pass with a per-row offset and
+// per-row prior weights (eta = x . theta + eta_offset, IRLS weight omega w) for NT in {9, 10, 11, 12}.
+#include "irls_coop_impl.hpp"
+
+namespace dlsa {
+
+DLSA_COOP_UNIT(launch_irls_coop_pois_ofs_wgt_g3, FamPoisson, EX_OFS | EX_WGT, 9, 10, 11, 12)
+
+}  // namespace dlsa

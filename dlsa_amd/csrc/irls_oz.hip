@@ -5,12 +5,12 @@
 
 namespace dlsa {
 
-// entry point, families, offset, first and last NT
-#define DLSA_OZ_UNITS(U)                         \
-  U(launch_irls_oz_g1, FamLogistic, false, 1, 6) \
-  U(launch_irls_oz_g2, FamLogistic, false, 7, 7)
-#define DLSA_DECLARE(name, fams, ofs, lo, hi) OzUnitFn name;
-#define DLSA_ROW(name, fams, ofs, lo, hi) {fams::mask, ofs, lo, hi, name},
+// entry point, families, row extras (none: no int8 pass with any), first and last NT
+#define DLSA_OZ_UNITS(U)                           \
+  U(launch_irls_oz_g1, FamLogistic, EX_NONE, 1, 6) \
+  U(launch_irls_oz_g2, FamLogistic, EX_NONE, 7, 7)
+#define DLSA_DECLARE(name, fams, ex, lo, hi) OzUnitFn name;
+#define DLSA_ROW(name, fams, ex, lo, hi) {fams::mask, ex, lo, hi, name},
 DLSA_OZ_UNITS(DLSA_DECLARE)
 static const UnitRow<OzUnitFn> kOzUnits[] = {DLSA_OZ_UNITS(DLSA_ROW)};
 
@@ -25,7 +25,7 @@ hipError_t launch_irls_oz(const PassArgs& a, int NT, bool standardize, int famil
                           hipStream_t s) {
   if (!family_rules(family).digit_scales) return hipErrorInvalidValue;
   if (!oz_applies(NT, a.p) || !a.colmax || !a.zcolmax || !a.theta_rec) return hipErrorInvalidValue;
-  OzUnitFn* unit = find_unit(kOzUnits, family, false, NT);
+  OzUnitFn* unit = find_unit(kOzUnits, family, EX_NONE, NT);
   return unit ? unit(a, NT, standardize, family, n_chunks, s) : hipErrorInvalidValue;
 }
 

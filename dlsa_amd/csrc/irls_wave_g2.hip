@@ -3,6 +3,6 @@
 
 namespace dlsa {
 
-DLSA_WAVE_UNIT(launch_irls_wave_g2, FamLogisticGaussian, false, 7, 8)
+DLSA_WAVE_UNIT(launch_irls_wave_g2, FamLogisticGaussian, EX_NONE, 7, 8)
 
 }  // namespace dlsa

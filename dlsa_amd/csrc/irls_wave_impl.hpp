@@ -121,18 +121,18 @@ __device__ __forceinline__ double wv_log12(double t) {
 // profiles/r04h_ols_ab.txt).
 constexpr int kWaveSlots = 2;
 // Ring slot: [16 B pad][npieces KiB of X rows][256 B: y of up to 32 rows]
-// (ofs, the Poisson pass with a per-row offset: [256 B: the rows' offsets])
+// (then 256 B per row extra, EX_*: the rows' offsets, the rows' prior weights)
 __host__ __device__ __forceinline__ int wave_npieces(int RB, int p) {
   return (RB * p * 8 + 16 + 1023) / 1024;
 }
-__host__ __device__ __forceinline__ int wave_slot_bytes_impl(int RB, int p, bool ofs = false) {
-  return 16 + wave_npieces(RB, p) * 1024 + 256 + (ofs ? 256 : 0);
+__host__ __device__ __forceinline__ int wave_slot_bytes_impl(int RB, int p, int n_extras = 0) {
+  return 16 + wave_npieces(RB, p) * 1024 + 256 + n_extras * 256;
 }
 // LDS of one workgroup: 2 ring slots + w of a block [RB] + theta [PMAX] +
 // center / 1/scale [2][PMAX]
 __host__ __device__ __forceinline__ int wave_lds_bytes_impl(int NT, int RB, int p,
-                                                            bool ofs = false) {
-  return kWaveSlots * wave_slot_bytes_impl(RB, p, ofs) + RB * 8 + 3 * 16 * NT * 8;
+                                                            int n_extras = 0) {
+  return kWaveSlots * wave_slot_bytes_impl(RB, p, n_extras) + RB * 8 + 3 * 16 * NT * 8;
 }
 
 // Waves per workgroup.  W = 2 (P <= 112): the T tiles are split over two
@@ -262,16 +262,21 @@ struct WaveCtx {
   int nrows, nb, npieces, slot_bytes, slot_y, part, chunk;
   __amdgpu_buffer_rsrc_t xr, yr;
   uintptr_t xcb;
-  __amdgpu_buffer_rsrc_t orr;  // OFS: the chunk's rows of a.eta_offset
+  __amdgpu_buffer_rsrc_t orr;  // EX_OFS: the chunk's rows of a.eta_offset
+  __amdgpu_buffer_rsrc_t wrr;  // EX_WGT: the chunk's rows of a.row_weight
 };
 
 // The block loop + epilogue of wave WID (a separate code path per wave: no
 // branch merges of the accumulator arrays).
-// OFS (FAMILY_POISSON only): eta = x . theta + a.eta_offset[row], streamed
-// like y into the 256 B behind it.
-template <int NT, int NS, int W, int WID, bool STD, int FAM, bool OFS = false>
+// EX (row extras, EX_* mask), each streamed like y into 256 B behind it, the
+// offset first: EX_OFS (FAMILY_POISSON only) eta = x . theta +
+// a.eta_offset[row]; EX_WGT prior weights omega = a.row_weight[row], which
+// multiply w, r and the row's log-likelihood terms once, after mu.
+template <int NT, int NS, int W, int WID, bool STD, int FAM, int EX = EX_NONE>
 __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, char* smem) {
   using TL = WaveTiles<NT, NS, W, WID>;
+  constexpr bool OFS = (EX & EX_OFS) != 0, WGT = (EX & EX_WGT) != 0;
+  constexpr int WOFF = 32 * (1 + (OFS ? 1 : 0));  // doubles from y to the weights in a slot
   // strip tiles (the last tile row as NS 4x4x4_4b sub-blocks)
   constexpr auto strip = [](int I) { return NS > 0 && I == NT - 1; };
   constexpr bool HAS_STRIP = NS > 0 && ((TL::RM >> (NT - 1)) & 1u);
@@ -332,6 +337,11 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
       if (WID == W - 1)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.orr, (lds_void_t*)(sbase + cx.slot_y + 256),
                                                  4, lane * 4, blk * RB * 8, 0, 0);
+    if constexpr (WGT)
+      if (WID == W - 1)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.wrr,
+                                                 (lds_void_t*)(sbase + cx.slot_y + WOFF * 8), 4,
+                                                 lane * 4, blk * RB * 8, 0, 0);
   };
 
   const int fl = lane & 15, q = lane >> 4;
@@ -396,6 +406,10 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
       // next partition's, even NaN) stays behind the selects on `valid`
       if constexpr (OFS) e += ys[32 + row];
       const double yv = ys[row];
+      // the prior weight, selected on `valid`: a padded row's is the next
+      // partition's (possibly NaN) and reaches nothing
+      [[maybe_unused]] double om = 1.0;
+      if constexpr (WGT) om = valid ? ys[WOFF + row] : 0.0;
       double w, r;
       if constexpr (FAM == FAMILY_LOGISTIC) {
         const double ea = exp(-fabs(e));
@@ -403,7 +417,12 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
         const double mu = e >= 0.0 ? inv : ea * inv;
         w = ea * inv * inv;  // mu (1 - mu), cancellation free
         r = yv - mu;
-        if (valid && sl == 0) llacc += yv * e - (fmax(e, 0.0) + wv_log12(1.0 + ea));
+        if (valid && sl == 0) {
+          if constexpr (WGT)
+            llacc += om * (yv * e - (fmax(e, 0.0) + wv_log12(1.0 + ea)));
+          else
+            llacc += yv * e - (fmax(e, 0.0) + wv_log12(1.0 + ea));
+        }
       } else if constexpr (FAM == FAMILY_POISSON) {
         // log link: mu = w = exp(eta); a padded row's eta is never
         // exponentiated.  llacc is the constant-free sum y eta - mu (what the
@@ -413,13 +432,22 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
         w = mu;
         r = yv - mu;
         if (valid && sl == 0) {
-          llacc += yv * e - mu;
-          if (yv != 0.0 && yv != 1.0) llcacc -= lgamma1p(yv);  // 0 at y = 0, 1
+          if constexpr (WGT) {
+            llacc += om * (yv * e - mu);
+            if (yv != 0.0 && yv != 1.0) llcacc -= om * lgamma1p(yv);
+          } else {
+            llacc += yv * e - mu;
+            if (yv != 0.0 && yv != 1.0) llcacc -= lgamma1p(yv);  // 0 at y = 0, 1
+          }
         }
       } else {  // gaussian (OLS): mu = eta, w = 1, ll = -rss / 2
         w = 1.0;
         r = yv - e;
         if (valid && sl == 0) llacc -= 0.5 * r * r;
+      }
+      if constexpr (WGT) {  // once, after mu; ahead of the padded rows' zeroing
+        w *= om;
+        r *= om;
       }
       if (!valid) {
         w = 0.0;
@@ -560,9 +588,10 @@ constexpr int wave_min_waves(int NT, int W, int FAM) {
   return W == 1 ? 1 : (NT <= 4 && FAM == FAMILY_GAUSSIAN ? 5 : 2);
 }
 
-template <int NT, int NS, int W, bool STD, int FAM, bool OFS = false>
+template <int NT, int NS, int W, bool STD, int FAM, int EX = EX_NONE>
 __global__ __launch_bounds__(64 * W, wave_min_waves(NT, W, FAM)) void irls_wave_kernel(
-    const typename pass_args_of<OFS>::type a) {
+    const typename pass_args_of<EX>::type a) {
+  constexpr bool OFS = (EX & EX_OFS) != 0, WGT = (EX & EX_WGT) != 0;
   static_assert(!OFS || FAM == FAMILY_POISSON, "the offset is the Poisson family's");
   constexpr int RB = wave_rb(NT, W, FAM);
   constexpr int PMAX = 16 * NT;
@@ -579,7 +608,7 @@ __global__ __launch_bounds__(64 * W, wave_min_waves(NT, W, FAM)) void irls_wave_
   cx.nrows = __builtin_amdgcn_readfirstlane(a.chunk_rows[cx.chunk]);
   cx.nb = (cx.nrows + RB - 1) / RB;
   cx.npieces = wave_npieces(RB, p);
-  cx.slot_bytes = wave_slot_bytes_impl(RB, p, OFS);
+  cx.slot_bytes = wave_slot_bytes_impl(RB, p, ex_count(EX));
   cx.slot_y = 16 + cx.npieces * 1024;
   double* wv = (double*)(smem + kWaveSlots * cx.slot_bytes);
   double* bet = wv + RB;
@@ -609,14 +638,18 @@ __global__ __launch_bounds__(64 * W, wave_min_waves(NT, W, FAM)) void irls_wave_
     const uintptr_t ocb = (uintptr_t)(a.eta_offset + cx.row0);
     cx.orr = uniform_rsrc(ocb, a.o_last4 + 4 - ocb);
   }
+  if constexpr (WGT) {
+    const uintptr_t wcb = (uintptr_t)(a.row_weight + cx.row0);
+    cx.wrr = uniform_rsrc(wcb, a.w_last4 + 4 - wcb);
+  }
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   if constexpr (W == 1) {
-    wave_body<NT, NS, 1, 0, STD, FAM, OFS>(a, cx, smem);
+    wave_body<NT, NS, 1, 0, STD, FAM, EX>(a, cx, smem);
   } else {
     if (wid == 0)
-      wave_body<NT, NS, W, 0, STD, FAM, OFS>(a, cx, smem);
+      wave_body<NT, NS, W, 0, STD, FAM, EX>(a, cx, smem);
     else
-      wave_body<NT, NS, W, 1, STD, FAM, OFS>(a, cx, smem);
+      wave_body<NT, NS, W, 1, STD, FAM, EX>(a, cx, smem);
   }
 }
 
@@ -627,59 +660,62 @@ static inline int wave_w(int NT, int requested = 0) {
   return wave_w_default(NT);
 }
 
-template <int NT, int W, bool STD, int FAM, bool OFS = false>
-static hipError_t launch_wave_t(const typename pass_args_of<OFS>::type& a, int n_chunks,
+template <int NT, int W, bool STD, int FAM, int EX = EX_NONE>
+static hipError_t launch_wave_t(const typename pass_args_of<EX>::type& a, int n_chunks,
                                 hipStream_t s) {
-  const size_t lds = wave_lds_bytes_impl(NT, wave_rb(NT, W, FAM), a.p, OFS);
+  const size_t lds = wave_lds_bytes_impl(NT, wave_rb(NT, W, FAM), a.p, ex_count(EX));
   switch (wave_strip_ns(NT, a.P)) {
     case 1:
-      hipLaunchKernelGGL((irls_wave_kernel<NT, 1, W, STD, FAM, OFS>), dim3(n_chunks), dim3(64 * W), lds,
+      hipLaunchKernelGGL((irls_wave_kernel<NT, 1, W, STD, FAM, EX>), dim3(n_chunks), dim3(64 * W), lds,
                          s, a);
       break;
     case 2:
-      hipLaunchKernelGGL((irls_wave_kernel<NT, 2, W, STD, FAM, OFS>), dim3(n_chunks), dim3(64 * W), lds,
+      hipLaunchKernelGGL((irls_wave_kernel<NT, 2, W, STD, FAM, EX>), dim3(n_chunks), dim3(64 * W), lds,
                          s, a);
       break;
     default:
-      hipLaunchKernelGGL((irls_wave_kernel<NT, 0, W, STD, FAM, OFS>), dim3(n_chunks), dim3(64 * W), lds,
+      hipLaunchKernelGGL((irls_wave_kernel<NT, 0, W, STD, FAM, EX>), dim3(n_chunks), dim3(64 * W), lds,
                          s, a);
   }
   return hipGetLastError();
 }
 
-template <int NT, bool STD, int FAM, bool OFS = false>
-static hipError_t launch_wave_sf(const typename pass_args_of<OFS>::type& a, int n_chunks,
+template <int NT, bool STD, int FAM, int EX = EX_NONE>
+static hipError_t launch_wave_sf(const typename pass_args_of<EX>::type& a, int n_chunks,
                                  hipStream_t s) {
   if constexpr (NT >= 2 && NT <= 7) {
-    if (wave_w(NT, a.waves) == 2) return launch_wave_t<NT, 2, STD, FAM, OFS>(a, n_chunks, s);
+    if (wave_w(NT, a.waves) == 2) return launch_wave_t<NT, 2, STD, FAM, EX>(a, n_chunks, s);
   }
-  return launch_wave_t<NT, 1, STD, FAM, OFS>(a, n_chunks, s);
+  return launch_wave_t<NT, 1, STD, FAM, EX>(a, n_chunks, s);
 }
 
-// The launcher of one (NT, family, offset), guarded by the family's rules.  A
-// kernel without an offset takes the PassArgs slice of `a`.
-template <int NT, int FAM, bool OFS>
-static hipError_t launch_wave_nt(const PassArgsOfs& a, bool std_, int n_chunks, hipStream_t s) {
+// The launcher of one (NT, family, row extras), guarded by the family's
+// rules.  A kernel takes the slice of `a` its extras need.
+template <int NT, int FAM, int EX>
+static hipError_t launch_wave_nt(const PassArgsWgt& a, bool std_, int n_chunks, hipStream_t s) {
   constexpr FamilyRules R = family_rules(FAM);
+  constexpr bool OFS = (EX & EX_OFS) != 0, WGT = (EX & EX_WGT) != 0;
   static_assert(!OFS || R.offset, "an offset kernel of a family without one");
+  static_assert(!WGT || R.weights, "a weighted kernel of a family without weights");
   if (R.sums_ll_const && !a.slab_llc) return hipErrorInvalidValue;
   if (OFS && !a.eta_offset) return hipErrorInvalidValue;
-  const typename pass_args_of<OFS>::type& ka = a;
-  return std_ ? launch_wave_sf<NT, true, FAM, OFS>(ka, n_chunks, s)
-              : launch_wave_sf<NT, false, FAM, OFS>(ka, n_chunks, s);
+  if (WGT && !a.row_weight) return hipErrorInvalidValue;
+  const typename pass_args_of<EX>::type& ka = a;
+  return std_ ? launch_wave_sf<NT, true, FAM, EX>(ka, n_chunks, s)
+              : launch_wave_sf<NT, false, FAM, EX>(ka, n_chunks, s);
 }
 
 // Entry point of a compilation unit, one line per unit:
-//   DLSA_WAVE_UNIT(name, family set (an IntList), OFS, NT...)
+//   DLSA_WAVE_UNIT(name, family set (an IntList), row extras (EX_* mask), NT...)
 // irls_wave.hip lists the units and routes to them.
-typedef hipError_t WaveUnitFn(const PassArgsOfs& a, int NT, bool std_, int family, int n_chunks,
+typedef hipError_t WaveUnitFn(const PassArgsWgt& a, int NT, bool std_, int family, int n_chunks,
                               hipStream_t s);
-#define DLSA_WAVE_UNIT(name, FAMS, OFS, ...)                                                  \
-  hipError_t name(const PassArgsOfs& a, int NT, bool std_, int family, int n_chunks,          \
+#define DLSA_WAVE_UNIT(name, FAMS, EX, ...)                                                   \
+  hipError_t name(const PassArgsWgt& a, int NT, bool std_, int family, int n_chunks,          \
                   hipStream_t s) {                                                            \
     return unit_dispatch(FAMS{}, IntList<__VA_ARGS__>{}, family, NT, [&](auto fam, auto nt) { \
-      return launch_wave_nt<decltype(nt)::value, decltype(fam)::value, OFS>(a, std_, n_chunks, \
-                                                                            s);               \
+      return launch_wave_nt<decltype(nt)::value, decltype(fam)::value, (EX)>(a, std_,         \
+                                                                             n_chunks, s);    \
     });                                                                                       \
   }
 

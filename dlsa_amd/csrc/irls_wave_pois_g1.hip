@@ -3,6 +3,6 @@
 
 namespace dlsa {
 
-DLSA_WAVE_UNIT(launch_irls_wave_pois_g1, FamPoisson, false, 1, 2, 3, 4, 5, 6)
+DLSA_WAVE_UNIT(launch_irls_wave_pois_g1, FamPoisson, EX_NONE, 1, 2, 3, 4, 5, 6)
 
 }  // namespace dlsa

@@ -3,6 +3,6 @@
 
 namespace dlsa {
 
-DLSA_WAVE_UNIT(launch_irls_wave_pois_g2, FamPoisson, false, 7, 8)
+DLSA_WAVE_UNIT(launch_irls_wave_pois_g2, FamPoisson, EX_NONE, 7, 8)
 
 }  // namespace dlsa

@@ -4,6 +4,6 @@
 
 namespace dlsa {
 
-DLSA_WAVE_UNIT(launch_irls_wave_pois_ofs_g1, FamPoisson, true, 1, 2, 3, 4, 5, 6)
+DLSA_WAVE_UNIT(launch_irls_wave_pois_ofs_g1, FamPoisson, EX_OFS, 1, 2, 3, 4, 5, 6)
 
 }  // namespace dlsa

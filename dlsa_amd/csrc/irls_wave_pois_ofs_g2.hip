@@ -4,6 +4,6 @@
 
 namespace dlsa {
 
-DLSA_WAVE_UNIT(launch_irls_wave_pois_ofs_g2, FamPoisson, true, 7, 8)
+DLSA_WAVE_UNIT(launch_irls_wave_pois_ofs_g2, FamPoisson, EX_OFS, 7, 8)
 
 }  // namespace dlsa

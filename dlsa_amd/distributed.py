@@ -89,29 +89,34 @@ def reduce_loglik(ll_kb, group=None):
 
 
 def loglik_sharded(X, y, offsets, betas, fit_intercept=False, center=None, scale=None,
-                   codes=None, levels=None, group=None):
+                   codes=None, levels=None, group=None, sample_weight=None):
     """Second pass of a sharded job (dlsa/model_eval.py:10-42): the
     log-likelihood of each candidate row of ``betas`` [B, P] over the whole
     data set.  X, y, offsets describe the LOCAL shard as in
     ``dlsa_fit_sharded`` (with ``codes``/``levels`` X holds the numeric columns
     of the categorical-code layout).  The local pass leaves the [B] total of
     this rank's partitions on the device; ONE all-reduce of those B doubles
-    gives every rank the global sums.  Returns a numpy [B] array."""
+    gives every rank the global sums.  Returns a numpy [B] array.
+    ``sample_weight``: the prior weights of the local shard's rows
+    (``logistic_loglik_batched``; dense layout only)."""
     from .models import logistic_loglik_batched, logistic_loglik_batched_categorical
 
+    if codes is not None and sample_weight is not None:
+        raise ValueError("sample_weight runs on the dense layout only (no codes)")
     if codes is not None:
         _, tot = logistic_loglik_batched_categorical(
             X, codes, y, offsets, levels, betas, fit_intercept=fit_intercept, center=center,
             scale=scale, return_sum=True)
     else:
         _, tot = logistic_loglik_batched(X, y, offsets, betas, fit_intercept=fit_intercept,
-                                         center=center, scale=scale, return_sum=True)
+                                         center=center, scale=scale, return_sum=True,
+                                         sample_weight=sample_weight)
     return combine(tot, group).cpu().numpy()
 
 
 def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
                      group=None, codes=None, levels=None, family="logistic", eta_offset=None,
-                     exposure=None, **fit_kw):
+                     exposure=None, sample_weight=None, **fit_kw):
     """Fit this rank's partitions on its GPU and return the global DLSA result.
 
     X, y, offsets describe the LOCAL shard (rows already on this rank's
@@ -124,15 +129,32 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
     ``eta_offset`` / ``exposure`` (family="poisson" only): the per-row offset
     of the local shard's rows (``poisson_model_batched_offset``); the combine
     step never sees it.
+    ``sample_weight``: per-row prior weights of the local shard's rows
+    (``logistic_model_batched_weighted`` / ``poisson_model_batched_weighted``;
+    dense layout only).  N, the DBIC's sample size, stays the ROW count: weights that are
+    precision or survey weights leave the number of observations unchanged.  A
+    frequency-weights user who wants N = sum of the weights calls
+    ``finish(..., n_global=)`` on the reduced sums directly.
     """
     from .models import (logistic_model_batched, logistic_model_batched_categorical,
-                         poisson_model_batched, poisson_model_batched_offset)
+                         logistic_model_batched_weighted, poisson_model_batched,
+                         poisson_model_batched_offset, poisson_model_batched_weighted)
 
     if family not in ("logistic", "poisson"):
         raise ValueError(f"family must be 'logistic' or 'poisson', not {family!r}")
     if (eta_offset is not None or exposure is not None) and family != "poisson":
         raise ValueError("eta_offset / exposure need family='poisson'")
-    if family == "poisson":
+    if sample_weight is not None:  # (None: exactly the unweighted calls below)
+        if codes is not None:
+            raise ValueError("sample_weight runs on the dense layout only (no codes)")
+        if family == "poisson":
+            fit = poisson_model_batched_weighted(X, y, offsets, sample_weight=sample_weight,
+                                                 eta_offset=eta_offset, exposure=exposure,
+                                                 fit_intercept=fit_intercept, **fit_kw)
+        else:
+            fit = logistic_model_batched_weighted(X, y, offsets, sample_weight=sample_weight,
+                                                  fit_intercept=fit_intercept, **fit_kw)
+    elif family == "poisson":
         if codes is not None:
             raise ValueError("family='poisson' runs on the dense layout only (no codes)")
         if eta_offset is not None or exposure is not None:

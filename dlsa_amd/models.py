@@ -302,6 +302,25 @@ def _check_eta_offset(X, eta_offset, exposure):
             raise ValueError("exposure must be finite and > 0 (drop the rows with none)")
 
 
+def _check_sample_weight(X, sample_weight):
+    """The argument checks of per-row prior weights, before anything touches
+    the GPU: n entries, every one finite and >= 0."""
+    if sample_weight is None:
+        return
+    n = int(X.shape[0]) if hasattr(X, "shape") else int(np.shape(X)[0])
+    v = sample_weight
+    is_t = torch is not None and isinstance(v, torch.Tensor)
+    if (int(v.numel()) if is_t else int(np.size(v))) != n:
+        raise ValueError("sample_weight must have n entries (one per row of X)")
+    if is_t:
+        ok = bool((torch.isfinite(v) & (v >= 0)).all())
+    else:
+        a = np.asarray(v, dtype=np.float64)
+        ok = bool(np.isfinite(a).all() and (a >= 0).all())
+    if not ok:
+        raise ValueError("sample_weight must be finite and >= 0")
+
+
 def _dev_eta_offset(eta_offset, exposure, dev):
     """[n] fp64 offset on the device (log exposure taken there), or None."""
     if exposure is not None:
@@ -312,18 +331,26 @@ def _dev_eta_offset(eta_offset, exposure, dev):
 def _glm_model_batched(entry, X, y, offsets, fit_intercept, center, scale, max_iter, tol,
                        hessian, switch_tol, record_timing, rows_per_chunk, workspace, device,
                        exact, exact_waves, oz_max_bytes, with_offset=False, eta_offset=None,
-                       exposure=None):
+                       exposure=None, sample_weight=None, weighted_entry=None):
     """The body the iterative families share: checked device copies, outputs,
     options and workspace, then the C-ABI call ``entry`` (an ``*_fit_batched_ex``
     symbol, or with ``with_offset`` one that takes ``eta_offset`` after y: the
     pointer is null when neither ``eta_offset`` nor ``exposure`` is given).
+    With ``sample_weight`` the call is ``weighted_entry`` instead, which takes
+    the weights after y (after ``eta_offset`` when ``with_offset``).
     Returns a BatchedFit."""
     if with_offset:
         _check_eta_offset(X, eta_offset, exposure)
+    _check_sample_weight(X, sample_weight)
     dev = _require_gpu(device)
     Xd = _dev_f64(X, dev)
     yd = _dev_f64(y, dev).reshape(-1)
     od = _dev_eta_offset(eta_offset, exposure, dev) if with_offset else None
+    extra = [_ptr(od)] if with_offset else []
+    if sample_weight is not None:
+        wd = _dev_f64(sample_weight, dev).reshape(-1)
+        entry = weighted_entry
+        extra.append(_ptr(wd))
     if Xd.dim() != 2:
         raise ValueError("X must be 2-D [n, p]")
     n, p = Xd.shape
@@ -369,7 +396,7 @@ def _glm_model_batched(entry, X, y, offsets, fit_intercept, center, scale, max_i
     opt.workspace = workspace.data_ptr()
     opt.workspace_bytes = workspace.numel()
     rc = getattr(lib, entry)(
-        _ptr(Xd), _ptr(yd), *([_ptr(od)] if with_offset else []), offs_p, K, p,
+        _ptr(Xd), _ptr(yd), *extra, offs_p, K, p,
         int(bool(fit_intercept)), _ptr(cd), _ptr(sd),
         int(max_iter), float(tol), _ptr(theta), _ptr(sig), _ptr(sigt), _ptr(ll), _ptr(iters),
         _ptr(status), ctypes.byref(opt), _stream(dev))
@@ -406,6 +433,31 @@ def logistic_model_batched(X, y, offsets, fit_intercept=False, center=None, scal
     return _glm_model_batched("dlsa_logistic_fit_batched_ex", X, y, offsets, fit_intercept, center,
                               scale, max_iter, tol, hessian, switch_tol, record_timing,
                               rows_per_chunk, workspace, device, exact, exact_waves, oz_max_bytes)
+
+
+def logistic_model_batched_weighted(X, y, offsets, sample_weight=None, fit_intercept=False,
+                                    center=None, scale=None, max_iter=100, tol=1e-10,
+                                    hessian="mixed", switch_tol=1e-6, record_timing=False,
+                                    rows_per_chunk=0, workspace=None, device=None, exact_waves=0):
+    """``logistic_model_batched`` with per-row prior weights.
+
+    ``sample_weight`` [n] (None: exactly the unweighted call): per-row prior
+    weights omega, finite and >= 0 (``ValueError`` otherwise, or for a wrong
+    length), as R's ``glm(weights=)``: the IRLS weight is omega w, the score
+    sum omega (y - mu) x, ``Sig_inv = X^T diag(omega w) X`` and ``loglik = sum
+    omega l_i``.  omega = 0 drops a row (its x and y must still be finite).  y
+    is used as given: y = s / m with omega = m is the grouped-binomial fit
+    (without the binomial-coefficient constant in loglik).  A partition whose
+    weights sum to 0 gets status "singular".  Weighted fits run on the fused
+    path only (P <= 192, ``DlsaHipError`` above) and take their exact passes
+    on the fp64 MFMA (there is no ``exact``; stats ``passes_oz`` stays 0)
+    (``dlsa_logistic_fit_batched_weighted``).
+    """
+    return _glm_model_batched("dlsa_logistic_fit_batched_ex", X, y, offsets, fit_intercept, center,
+                              scale, max_iter, tol, hessian, switch_tol, record_timing,
+                              rows_per_chunk, workspace, device, "auto", exact_waves, 0,
+                              sample_weight=sample_weight,
+                              weighted_entry="dlsa_logistic_fit_batched_weighted")
 
 
 def poisson_model_batched(X, y, offsets, fit_intercept=False, center=None, scale=None,
@@ -452,6 +504,28 @@ def poisson_model_batched_offset(X, y, offsets, eta_offset=None, exposure=None,
                               center, scale, max_iter, tol, hessian, switch_tol, record_timing,
                               rows_per_chunk, workspace, device, "auto", exact_waves, 0,
                               with_offset=True, eta_offset=eta_offset, exposure=exposure)
+
+
+def poisson_model_batched_weighted(X, y, offsets, sample_weight=None, eta_offset=None,
+                                   exposure=None, fit_intercept=False, center=None, scale=None,
+                                   max_iter=100, tol=1e-10, hessian="mixed", switch_tol=1e-6,
+                                   record_timing=False, rows_per_chunk=0, workspace=None,
+                                   device=None, exact_waves=0):
+    """``poisson_model_batched`` / ``poisson_model_batched_offset`` with per-row
+    prior weights omega = ``sample_weight`` [n], finite and >= 0 (``ValueError``
+    otherwise, or for a wrong length; None: exactly the unweighted call), as
+    in ``logistic_model_batched_weighted``: ``Sig_inv = X^T diag(omega mu) X``,
+    ``loglik = sum omega (y eta - mu - lgamma(y + 1))``.  With an intercept the
+    fit starts at log(sum omega y / sum omega exp(eta_offset)); a partition
+    with sum omega = 0 or sum omega y = 0 gets status "singular", all-zero
+    outputs (``dlsa_poisson_fit_batched_weighted``).  ``eta_offset`` /
+    ``exposure`` are optional, as in ``poisson_model_batched_offset``."""
+    return _glm_model_batched("dlsa_poisson_fit_batched_offset", X, y, offsets, fit_intercept,
+                              center, scale, max_iter, tol, hessian, switch_tol, record_timing,
+                              rows_per_chunk, workspace, device, "auto", exact_waves, 0,
+                              with_offset=True, eta_offset=eta_offset, exposure=exposure,
+                              sample_weight=sample_weight,
+                              weighted_entry="dlsa_poisson_fit_batched_weighted")
 
 
 def _cat_inputs(Xn, codes, y, offsets, levels, center, scale, dev):
@@ -600,16 +674,24 @@ def _loglik_groups(call, betas, P, K, dev, return_sum):
 
 
 def _loglik_dense(entry, X, y, offsets, betas, fit_intercept, center, scale, device, return_sum,
-                  with_offset=False, eta_offset=None, exposure=None):
+                  with_offset=False, eta_offset=None, exposure=None, sample_weight=None,
+                  weighted_entry=None):
     """The dense evaluation pass of one family (``entry``: a
     ``*_loglik_batched_sum`` symbol, or with ``with_offset`` one that takes
-    ``eta_offset`` after y) through ``_loglik_groups``."""
+    ``eta_offset`` after y; with ``sample_weight`` ``weighted_entry``, which
+    takes the weights behind those) through ``_loglik_groups``."""
     if with_offset:
         _check_eta_offset(X, eta_offset, exposure)
+    _check_sample_weight(X, sample_weight)
     dev = _require_gpu(device)
     Xd = _dev_f64(X, dev)
     yd = _dev_f64(y, dev).reshape(-1)
     od = _dev_eta_offset(eta_offset, exposure, dev) if with_offset else None
+    extra = [_ptr(od)] if with_offset else []
+    if sample_weight is not None:
+        wd = _dev_f64(sample_weight, dev).reshape(-1)
+        entry = weighted_entry
+        extra.append(_ptr(wd))
     n, p = Xd.shape
     offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
     K = offs.size - 1
@@ -622,7 +704,7 @@ def _loglik_dense(entry, X, y, offsets, betas, fit_intercept, center, scale, dev
     fn = getattr(_hip.load(), entry)
 
     def call(bd, g, out, total):
-        rc = fn(_ptr(Xd), _ptr(yd), *([_ptr(od)] if with_offset else []),
+        rc = fn(_ptr(Xd), _ptr(yd), *extra,
                 offs.ctypes.data_as(ctypes.c_void_p), K, p, int(bool(fit_intercept)), _ptr(cd), _ptr(sd), _ptr(bd), g, _ptr(out), _ptr(total),
                 _stream(dev))
         _hip.check(rc, entry)
@@ -631,15 +713,19 @@ def _loglik_dense(entry, X, y, offsets, betas, fit_intercept, center, scale, dev
 
 
 def logistic_loglik_batched(X, y, offsets, betas, fit_intercept=False, center=None, scale=None,
-                            device=None, return_sum=False):
+                            device=None, return_sum=False, sample_weight=None):
     """Per-partition log-likelihood of candidate coefficient vectors in one
     pass over X (the evaluation step of dlsa/models.py:151-225 /
     dlsa/model_eval.py:10-42).  betas: [B, P], intercept first; more than 16
     candidates are evaluated 16 to a pass.  Returns a [K, B] fp64 tensor on
     the device; with ``return_sum`` also its [B] sum over the partitions (the
-    group-by sum of model_eval.py:38, fixed order, on the device)."""
+    group-by sum of model_eval.py:38, fixed order, on the device).
+    ``sample_weight`` [n] (None: exactly the unweighted call): every row's term
+    is multiplied by its prior weight, the log-likelihood of the weighted fit
+    (finite and >= 0, n entries, else ``ValueError``)."""
     return _loglik_dense("dlsa_logistic_loglik_batched_sum", X, y, offsets, betas, fit_intercept,
-                         center, scale, device, return_sum)
+                         center, scale, device, return_sum, sample_weight=sample_weight,
+                         weighted_entry="dlsa_logistic_loglik_batched_sum_weighted")
 
 
 def poisson_loglik_batched(X, y, offsets, betas, fit_intercept=False, center=None, scale=None,
@@ -663,6 +749,20 @@ def poisson_loglik_batched_offset(X, y, offsets, betas, eta_offset=None, exposur
     return _loglik_dense("dlsa_poisson_loglik_batched_sum_offset", X, y, offsets, betas,
                          fit_intercept, center, scale, device, return_sum, with_offset=True,
                          eta_offset=eta_offset, exposure=exposure)
+
+
+def poisson_loglik_batched_weighted(X, y, offsets, betas, sample_weight=None, eta_offset=None,
+                                    exposure=None, fit_intercept=False, center=None, scale=None,
+                                    device=None, return_sum=False):
+    """``poisson_loglik_batched`` / ``poisson_loglik_batched_offset`` with the
+    prior weights of ``poisson_model_batched_weighted``: every row's term, the
+    constant -lgamma(y + 1) included, is multiplied by ``sample_weight`` [n]
+    (finite and >= 0, else ``ValueError``; None: exactly the unweighted call)
+    (``dlsa_poisson_loglik_batched_sum_weighted``)."""
+    return _loglik_dense("dlsa_poisson_loglik_batched_sum_offset", X, y, offsets, betas,
+                         fit_intercept, center, scale, device, return_sum, with_offset=True,
+                         eta_offset=eta_offset, exposure=exposure, sample_weight=sample_weight,
+                         weighted_entry="dlsa_poisson_loglik_batched_sum_weighted")
 
 
 def logistic_loglik_batched_categorical(Xn, codes, y, offsets, levels, betas, fit_intercept=False,

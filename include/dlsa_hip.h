@@ -315,6 +315,93 @@ int dlsa_poisson_loglik_batched_sum_offset(const double* X, const double* y,
                                            void* stream);
 
 /*
+ * Per-row prior weights omega (R's glm(weights=), sample_weight /
+ * freq_weights elsewhere) for the logistic and Poisson fits, per partition:
+ *   eta and mu are unchanged; the IRLS weight is omega_i w_i, the score
+ *   sum_i omega_i (y_i - mu_i) x_i, sig_inv = X^T diag(omega w) X at the
+ *   returned theta, loglik = sum_i omega_i l_i with l_i the unweighted entry's
+ *   per-row term (Poisson: including -omega_i lgamma(y_i + 1)).
+ *  row_weight  [n_total] fp64, device, finite and >= 0; row i belongs to row i
+ *              of X.  NULL: exactly the unweighted entry
+ *              (dlsa_logistic_fit_batched_ex, dlsa_poisson_fit_batched_offset):
+ *              the same kernels, bit-identical outputs.
+ * omega_i = 0 drops the row from the fit, but its x and y must still be
+ * finite: 0 * NaN is NaN, so a non-finite x ends the partition
+ * DLSA_STATUS_NONFINITE as in the unweighted fit.
+ * Logistic y is used as given: with y_i = s_i / m_i and omega_i = m_i this is
+ * the grouped-binomial fit (s_i successes of m_i trials per row) without the
+ * binomial-coefficient constant sum_i log C(m_i, s_i) in loglik.
+ * All other arguments and the outputs as in the unweighted entries; eta_offset
+ * of the Poisson entry may be NULL.  The weights are one more 8 B/row stream
+ * of the passes; nothing per row is stored and the workspace
+ * (dlsa_logistic_workspace_bytes) is unchanged.
+ * Statuses, decided by one pass over omega before any Newton pass: a partition
+ * with a negative or non-finite omega ends DLSA_STATUS_NONFINITE, one with
+ * sum omega = 0 (Poisson: or sum omega y = 0) DLSA_STATUS_SINGULAR, both with
+ * all-zero outputs; the other partitions are not affected.
+ * Start point: logistic theta = 0; Poisson with an intercept theta =
+ * (log(sum omega y / sum omega exp(eta_offset)), 0, ..., 0), the MLE of the
+ * weighted intercept-only model, to which restarts go back.
+ * Limits (each a follow-up):
+ *   - the fused path on the dense layout only: P = p + intercept <=
+ *     DLSA_MAX_P_FUSED (192), else DLSA_E_UNSUPPORTED before any launch (no
+ *     weighted wide path);
+ *   - no weights on the categorical layout (dlsa_logistic_fit_categorical) nor
+ *     for OLS (dlsa_ols_fit_batched);
+ *   - no int8 exact pass: the exact passes of a weighted fit run on the fp64
+ *     MFMA whatever opt->exact_pass says (the digit-grid bound of the int8
+ *     pass relies on sqrt(w) <= 1/2, which omega breaks); dlsa_fit_stats
+ *     passes_oz stays 0.
+ */
+int dlsa_logistic_fit_batched_weighted(const double* X, const double* y,
+                                       const double* row_weight,
+                                       const int64_t* offsets, int32_t K, int32_t p,
+                                       int32_t fit_intercept, const double* center,
+                                       const double* scale, int32_t max_iter,
+                                       double tol, double* theta, double* sig_inv,
+                                       double* sig_inv_theta, double* loglik,
+                                       int32_t* iters, int32_t* status,
+                                       const dlsa_fit_options* opt, void* stream);
+int dlsa_poisson_fit_batched_weighted(const double* X, const double* y,
+                                      const double* eta_offset,
+                                      const double* row_weight,
+                                      const int64_t* offsets, int32_t K, int32_t p,
+                                      int32_t fit_intercept, const double* center,
+                                      const double* scale, int32_t max_iter,
+                                      double tol, double* theta, double* sig_inv,
+                                      double* sig_inv_theta, double* loglik,
+                                      int32_t* iters, int32_t* status,
+                                      const dlsa_fit_options* opt, void* stream);
+
+/*
+ * dlsa_logistic_loglik_batched_sum / dlsa_poisson_loglik_batched_sum_offset
+ * with the prior weights of the weighted fits:
+ *   loglik[k * n_beta + b] = sum_i omega_i l_ib
+ * (Poisson: l_ib includes -lgamma(y_i + 1); eta_offset may be NULL).
+ * row_weight [n_total] fp64, device; NULL: exactly the unweighted entry,
+ * bit-identical.  The weights are not checked here: a non-finite omega makes
+ * its partition's sums non-finite.  Same limits (P <= 512, 1 <= n_beta <= 16)
+ * and fixed summation order; dense layout only.
+ */
+int dlsa_logistic_loglik_batched_sum_weighted(const double* X, const double* y,
+                                              const double* row_weight,
+                                              const int64_t* offsets, int32_t K,
+                                              int32_t p, int32_t fit_intercept,
+                                              const double* center, const double* scale,
+                                              const double* betas, int32_t n_beta,
+                                              double* loglik, double* loglik_sum,
+                                              void* stream);
+int dlsa_poisson_loglik_batched_sum_weighted(const double* X, const double* y,
+                                             const double* eta_offset,
+                                             const double* row_weight,
+                                             const int64_t* offsets, int32_t K,
+                                             int32_t p, int32_t fit_intercept,
+                                             const double* center, const double* scale,
+                                             const double* betas, int32_t n_beta,
+                                             double* loglik, double* loglik_sum,
+                                             void* stream);
+
+/*
  * Batched local OLS fit (the linear DLSA path; the
  * reference only has a statsmodels per-group demo,
  * projects/results/linear_regression_dc.py:27-37):
