@@ -64,158 +64,60 @@ hipError_t launch_level_reset(int K, int P, int start_phase, int32_t* phase, int
   return hipGetLastError();
 }
 
-// Poisson start point, after fit_init: one workgroup per partition sums y in a
-// fixed order (thread t takes rows t, t + 256, ...; xor butterfly inside the
-// wave, then the four waves in index order: the same bits run to run) and
-// takes min y and a finiteness flag along.  With an intercept the fit starts
-// at the MLE of the intercept-only model, theta = (log mean y, 0, ..., 0):
-// from theta = 0 a Newton step at mean y ~ 50 overshoots to eta ~ 50.
-// Without an intercept the start stays theta = 0.  theta0[k] keeps the start
-// value of parameter 0 for the restarts (level_fail, level_reset_kernel).
-// A partition with a negative or non-finite y ends NONFINITE, one with
-// sum y = 0 (its MLE does not exist) SINGULAR, both before any pass and with
-// the zeroed outputs fit_init wrote.
-__global__ __launch_bounds__(256) void poisson_start_kernel(const double* y, const int64_t* offsets,
-                                                            int P, int intercept, double* theta,
-                                                            double* theta0, int32_t* phase,
-                                                            int32_t* status) {
-  __shared__ double ssum[4], smin[4];
-  __shared__ int sbad[4];
-  const int k = blockIdx.x;
-  const int64_t r0 = offsets[k], r1 = offsets[k + 1];
-  double sum = 0.0, mn = INFINITY;
-  int bad = 0;
-  for (int64_t i = r0 + threadIdx.x; i < r1; i += 256) {
-    const double v = y[i];
-    bad |= !isfinite(v);
-    sum += v;
-    mn = fmin(mn, v);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sum += __shfl_xor(sum, o);
-    mn = fmin(mn, __shfl_xor(mn, o));
-    bad |= __shfl_xor(bad, o);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    ssum[threadIdx.x >> 6] = sum;
-    smin[threadIdx.x >> 6] = mn;
-    sbad[threadIdx.x >> 6] = bad;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  sum = ((ssum[0] + ssum[1]) + ssum[2]) + ssum[3];
-  mn = fmin(fmin(smin[0], smin[1]), fmin(smin[2], smin[3]));
-  bad = sbad[0] | sbad[1] | sbad[2] | sbad[3];
-  theta0[k] = 0.0;
-  if (r1 <= r0) return;  // empty: fit_init's DLSA_STATUS_EMPTY stands
-  if (bad || !(mn >= 0.0) || !isfinite(sum)) {
-    status[k] = DLSA_STATUS_NONFINITE;
-    phase[k] = PHASE_DONE;
-  } else if (!(sum > 0.0)) {
-    status[k] = DLSA_STATUS_SINGULAR;
-    phase[k] = PHASE_DONE;
-  } else if (intercept) {
-    const double t0 = log(sum / (double)(r1 - r0));
-    theta0[k] = t0;
-    theta[(int64_t)k * P] = t0;
-  }
+// What the pre-pass makes of a non-empty partition's sums: the status that
+// ends it, or STATUS_RUNNING.  bad: a non-finite y, o or omega; mn: min over y
+// and omega; sw = sum omega, swy = sum omega y, swe = sum omega exp(o) (sum
+// omega without an offset; swy = swe = 0 for a family without a device start).
+//   NONFINITE  a bad or negative entry, or a sum that is not finite
+//   SINGULAR   sum omega = 0, or (Poisson) sum omega y = 0: no MLE
+//   NONFINITE  (Poisson) sum omega exp(o) = 0 or a quotient that is not
+//              finite: no finite start
+// A partition with sum omega y = 0 and sum omega exp(o) = 0 (every exp(o)
+// underflowed) meets both of the last two: the weighted entries report it
+// SINGULAR, the unweighted ones NONFINITE, a documented difference between
+// them that callers may rely on.
+__device__ __forceinline__ int prepass_status(bool poisson, bool weighted, int bad, double mn,
+                                              double sw, double swy, double swe) {
+  if (bad || !(mn >= 0.0) || !isfinite(sw) || !isfinite(swy) || !isfinite(swe))
+    return DLSA_STATUS_NONFINITE;
+  const bool singular = !(sw > 0.0) || (poisson && !(swy > 0.0));
+  const bool no_start = poisson && (!(swe > 0.0) || !isfinite(swy / swe));
+  if (singular && no_start) return weighted ? DLSA_STATUS_SINGULAR : DLSA_STATUS_NONFINITE;
+  return singular ? DLSA_STATUS_SINGULAR : no_start ? DLSA_STATUS_NONFINITE : STATUS_RUNNING;
 }
 
-// The start point with a per-row offset o (eta = x . theta + o): the same
-// fixed-order pass also sums exp(o) and checks o.  With an intercept the fit
-// starts at theta = (log(sum y / sum exp(o)), 0, ..., 0), the MLE of the
-// intercept-only rate model; without one at 0.  A non-finite o, or a sum
-// exp(o) that is not finite and positive (no finite start exists), ends the
-// partition NONFINITE like a bad y.
-__global__ __launch_bounds__(256) void poisson_start_ofs_kernel(
-    const double* y, const double* eta_offset, const int64_t* offsets, int P, int intercept,
-    double* theta, double* theta0, int32_t* phase, int32_t* status) {
-  __shared__ double ssum[4], sexp[4], smin[4];
-  __shared__ int sbad[4];
-  const int k = blockIdx.x;
-  const int64_t r0 = offsets[k], r1 = offsets[k + 1];
-  double sum = 0.0, se = 0.0, mn = INFINITY;
-  int bad = 0;
-  for (int64_t i = r0 + threadIdx.x; i < r1; i += 256) {
-    const double v = y[i], o = eta_offset[i];
-    bad |= !isfinite(v) | !isfinite(o);
-    sum += v;
-    se += exp(o);
-    mn = fmin(mn, v);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sum += __shfl_xor(sum, o);
-    se += __shfl_xor(se, o);
-    mn = fmin(mn, __shfl_xor(mn, o));
-    bad |= __shfl_xor(bad, o);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    ssum[threadIdx.x >> 6] = sum;
-    sexp[threadIdx.x >> 6] = se;
-    smin[threadIdx.x >> 6] = mn;
-    sbad[threadIdx.x >> 6] = bad;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  sum = ((ssum[0] + ssum[1]) + ssum[2]) + ssum[3];
-  se = ((sexp[0] + sexp[1]) + sexp[2]) + sexp[3];
-  mn = fmin(fmin(smin[0], smin[1]), fmin(smin[2], smin[3]));
-  bad = sbad[0] | sbad[1] | sbad[2] | sbad[3];
-  theta0[k] = 0.0;
-  if (r1 <= r0) return;  // empty: fit_init's DLSA_STATUS_EMPTY stands
-  if (bad || !(mn >= 0.0) || !isfinite(sum) || !isfinite(se) || !(se > 0.0) ||
-      !isfinite(sum / se)) {
-    status[k] = DLSA_STATUS_NONFINITE;
-    phase[k] = PHASE_DONE;
-  } else if (!(sum > 0.0)) {
-    status[k] = DLSA_STATUS_SINGULAR;
-    phase[k] = PHASE_DONE;
-  } else if (intercept) {
-    const double t0 = log(sum / se);
-    theta0[k] = t0;
-    theta[(int64_t)k * P] = t0;
-  }
-}
-
-hipError_t launch_poisson_start(const double* y, const int64_t* offsets_dev, int K, int P,
-                                int intercept, double* theta, double* theta0, int32_t* phase,
-                                int32_t* status, hipStream_t s, const double* eta_offset) {
-  if (K <= 0) return hipSuccess;
-  if (eta_offset) {
-    hipLaunchKernelGGL(poisson_start_ofs_kernel, dim3(K), dim3(256), 0, s, y, eta_offset,
-                       offsets_dev, P, intercept, theta, theta0, phase, status);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(poisson_start_kernel, dim3(K), dim3(256), 0, s, y, offsets_dev, P, intercept,
-                     theta, theta0, phase, status);
-  return hipGetLastError();
-}
-
-// Pre-pass of a weighted fit, after fit_init: the fixed-order sum of
-// poisson_start_kernel over the partition's prior weights omega (and, for
-// Poisson, over omega y and omega exp(o); o = 0 without an offset).  A
-// negative or non-finite omega ends the partition NONFINITE and sum omega = 0
-// SINGULAR, before any pass and with the zeroed outputs fit_init wrote;
+// Pre-pass of a fit whose family starts from a device-computed point or that
+// carries prior weights, after fit_init: one workgroup per partition sums
+// omega, omega y and omega exp(o) in a fixed order (thread t takes rows t,
+// t + 256, ...; xor butterfly inside the wave, then the four waves in index
+// order: the same bits run to run) and takes min(y, omega) and a finiteness
+// flag along.  eta_offset and row_weight may be null (wave-uniform): without
+// weights omega is the literal 1, so omega y = y and omega exp(o) = exp(o)
+// exactly; without an offset no exp is evaluated and sum omega exp(o) is sum
+// omega (unweighted: the row count, which the fixed-order sum of ones gives
+// exactly).  A partition that prepass_status ends gets that status and
+// PHASE_DONE before any pass, with the zeroed outputs fit_init wrote;
 // nothing per row is stored.
-//   POISSON: also the checks of the unweighted start (y, o), sum omega y = 0
-//   ends the partition SINGULAR, and with an intercept the fit starts at
-//   theta = (log(sum omega y / sum omega exp(o)), 0, ..., 0), the MLE of the
-//   weighted intercept-only model (theta0[k] keeps it for the restarts).
-//   Logistic: statuses only; the start stays theta = 0.
+//   POISSON: with an intercept the fit starts at theta = (log(sum omega y /
+//   sum omega exp(o)), 0, ..., 0), the MLE of the intercept-only (rate)
+//   model: from theta = 0 a Newton step at mean y ~ 50 overshoots to eta ~
+//   50.  Without an intercept the start stays theta = 0.  theta0[k] keeps the
+//   start value of parameter 0 for the restarts (level_fail,
+//   level_reset_kernel).
+//   Otherwise (logistic, weighted): statuses only; y, eta_offset, theta and
+//   theta0 are not touched and the start stays theta = 0.
 template <bool POISSON>
-__global__ __launch_bounds__(256) void weight_start_kernel(
+__global__ __launch_bounds__(256) void fit_prepass_kernel(
     const double* y, const double* eta_offset, const double* row_weight, const int64_t* offsets,
     int P, int intercept, double* theta, double* theta0, int32_t* phase, int32_t* status) {
   __shared__ double ssw[4], sswy[4], sswe[4], smin[4];
   __shared__ int sbad[4];
   const int k = blockIdx.x;
   const int64_t r0 = offsets[k], r1 = offsets[k + 1];
-  double sw = 0.0, swy = 0.0, swe = 0.0, mn = INFINITY;  // mn: min over omega (and y)
+  double sw = 0.0, swy = 0.0, swe = 0.0, mn = INFINITY;
   int bad = 0;
   for (int64_t i = r0 + threadIdx.x; i < r1; i += 256) {
-    const double om = row_weight[i];
+    const double om = row_weight ? row_weight[i] : 1.0;
     bad |= !isfinite(om);
     sw += om;
     mn = fmin(mn, om);
@@ -258,39 +160,29 @@ __global__ __launch_bounds__(256) void weight_start_kernel(
     if (!eta_offset) swe = sw;
   }
   if (r1 <= r0) return;  // empty: fit_init's DLSA_STATUS_EMPTY stands
-  if (bad || !(mn >= 0.0) || !isfinite(sw) || !isfinite(swy) || !isfinite(swe)) {
-    status[k] = DLSA_STATUS_NONFINITE;
+  const int st = prepass_status(POISSON, row_weight != nullptr, bad, mn, sw, swy, swe);
+  if (st != STATUS_RUNNING) {
+    status[k] = st;
     phase[k] = PHASE_DONE;
-  } else if (!(sw > 0.0) || (POISSON && !(swy > 0.0))) {
-    status[k] = DLSA_STATUS_SINGULAR;
-    phase[k] = PHASE_DONE;
-  } else if constexpr (POISSON) {
-    if (!(swe > 0.0) || !isfinite(swy / swe)) {  // no finite start exists
-      status[k] = DLSA_STATUS_NONFINITE;
-      phase[k] = PHASE_DONE;
-    } else if (intercept) {
-      const double t0 = log(swy / swe);
-      theta0[k] = t0;
-      theta[(int64_t)k * P] = t0;
-    }
+  } else if (POISSON && intercept) {
+    const double t0 = log(swy / swe);
+    theta0[k] = t0;
+    theta[(int64_t)k * P] = t0;
   }
 }
 
-hipError_t launch_weight_check(const double* row_weight, const int64_t* offsets_dev, int K,
-                               int32_t* phase, int32_t* status, hipStream_t s) {
-  if (K <= 0) return hipSuccess;
-  hipLaunchKernelGGL(weight_start_kernel<false>, dim3(K), dim3(256), 0, s, nullptr, nullptr,
-                     row_weight, offsets_dev, 0, 0, nullptr, nullptr, phase, status);
-  return hipGetLastError();
-}
-
-hipError_t launch_poisson_start_wgt(const double* y, const double* eta_offset,
-                                    const double* row_weight, const int64_t* offsets_dev, int K,
-                                    int P, int intercept, double* theta, double* theta0,
-                                    int32_t* phase, int32_t* status, hipStream_t s) {
-  if (K <= 0) return hipSuccess;
-  hipLaunchKernelGGL(weight_start_kernel<true>, dim3(K), dim3(256), 0, s, y, eta_offset,
-                     row_weight, offsets_dev, P, intercept, theta, theta0, phase, status);
+hipError_t launch_fit_prepass(int family, const double* y, const double* eta_offset,
+                              const double* row_weight, const int64_t* offsets_dev, int K, int P,
+                              int intercept, double* theta, double* theta0, int32_t* phase,
+                              int32_t* status, hipStream_t s) {
+  const bool start = family_rules(family).device_start;
+  if (K <= 0 || (!start && !row_weight)) return hipSuccess;
+  if (start)
+    hipLaunchKernelGGL(fit_prepass_kernel<true>, dim3(K), dim3(256), 0, s, y, eta_offset,
+                       row_weight, offsets_dev, P, intercept, theta, theta0, phase, status);
+  else  // the weight check alone
+    hipLaunchKernelGGL(fit_prepass_kernel<false>, dim3(K), dim3(256), 0, s, nullptr, nullptr,
+                       row_weight, offsets_dev, 0, 0, nullptr, nullptr, phase, status);
   return hipGetLastError();
 }
 

@@ -264,7 +264,7 @@ static int loglik_dense(int family, const char* entry, const double* X, const do
   double* d_partial = (double*)ws.at(off_partial);
   DLSA_HIP_TRY(upload_eval_plan(pl, K, d_row0, d_rows, d_part, d_pcb, stream));
   if (pl.n_chunks > 0) {
-    EvalArgsWgt ea;  // (the unweighted kernels take its EvalArgs slice)
+    EvalArgsWgt ea;  // (each kernel takes its slice, launch_loglik_eval)
     memset(&ea, 0, sizeof(ea));
     ea.X = X;
     ea.y = y;
@@ -275,25 +275,18 @@ static int loglik_dense(int family, const char* entry, const double* X, const do
     ea.scale = scale;
     ea.betas = betas;
     ea.partial = d_partial;
-    const uintptr_t xend = (uintptr_t)(X + n_total * (int64_t)p);
-    ea.x_last16 = ((xend + 15) & ~(uintptr_t)15) - 16;
-    ea.y_last4 = (uintptr_t)(y + n_total) - 4;
     ea.eta_offset = eta_offset;
-    if (eta_offset) ea.o_last4 = (uintptr_t)(eta_offset + n_total) - 4;
+    ea.row_weight = row_weight;
     ea.p = p;
+    set_stream_bounds(ea, n_total);
     ea.P = P;
     ea.intercept = fit_intercept ? 1 : 0;
     ea.nbeta = n_beta;
-    ea.row_weight = row_weight;
-    if (row_weight) ea.w_last4 = (uintptr_t)(row_weight + n_total) - 4;
-    ea.slot_bytes = eval_slot_bytes(p, (eta_offset ? 1 : 0) + (row_weight ? 1 : 0));
+    ea.slot_bytes = eval_slot_bytes(p, ex_count(pass_extras(ea)));
     const int PM = ((P + 7) / 8) * 8;
     const int budget = 160 * 1024 - (n_beta * PM + 2 * PM + 64) * 8;
     ea.nslot = std::max(2, std::min(budget / ea.slot_bytes, 6));
-    if (row_weight)
-      DLSA_HIP_TRY(launch_loglik_eval_wgt(ea, family, pl.n_chunks, stream));
-    else
-      DLSA_HIP_TRY(launch_loglik_eval(ea, family, pl.n_chunks, stream));
+    DLSA_HIP_TRY(launch_loglik_eval(ea, family, pl.n_chunks, stream));
   }
   DLSA_HIP_TRY(launch_loglik_reduce(d_partial, d_pcb, K, n_beta, loglik, stream));
   if (loglik_sum) DLSA_HIP_TRY(launch_loglik_total(loglik, K, n_beta, loglik_sum, stream));

@@ -47,7 +47,7 @@ struct FamilyRules {
   bool digit_scales;
   // fp64 passes sum the log-likelihood's constant term into slab_llc
   bool sums_ll_const;
-  // starts from a device-computed point (launch_poisson_start), which may end partitions
+  // starts from a device-computed point (launch_fit_prepass), which may end partitions
   bool device_start;
   // may carry a per-row eta_offset (the EX_OFS kernels, PassArgsOfs)
   bool offset;
@@ -204,9 +204,23 @@ template <>
 struct pass_args_of<EX_OFS> {
   typedef PassArgsOfs type;
 };
-// the row-extras mask the dispatchers route on
-inline int pass_extras(const PassArgsWgt& a) {
+// the row-extras mask the dispatchers route on (A: PassArgsWgt or EvalArgsWgt)
+template <typename A>
+inline int pass_extras(const A& a) {
   return (a.eta_offset ? EX_OFS : 0) | (a.row_weight ? EX_WGT : 0);
+}
+// The bounds the LDS-DMA loads of a pass clamp their tail pieces to, so that
+// none reads past an array: the last readable 16 B of X and the last 4 B of y
+// and of each row extra the pass has (A: PassArgsWgt or EvalArgsWgt with X,
+// y, eta_offset, row_weight and p set; zeros stand for n_total = 0).
+template <typename A>
+inline void set_stream_bounds(A& a, int64_t n_total) {
+  if (n_total <= 0) return;
+  const uintptr_t xend = (uintptr_t)(a.X + n_total * (int64_t)a.p);
+  a.x_last16 = ((xend + 15) & ~(uintptr_t)15) - 16;
+  a.y_last4 = (uintptr_t)(a.y + n_total) - 4;
+  if (a.eta_offset) a.o_last4 = (uintptr_t)(a.eta_offset + n_total) - 4;
+  if (a.row_weight) a.w_last4 = (uintptr_t)(a.row_weight + n_total) - 4;
 }
 
 // A/B knobs of profiling builds.  The product library reads no environment
@@ -556,11 +570,10 @@ hipError_t launch_wide_assemble(const WideArgs& a, const int32_t* gcb, double* H
 hipError_t launch_wide_newton(const SolveArgs& sa, const WideArgs& wa, const int32_t* rcb,
                               const int32_t* gcb, double* Hfull, int K, hipStream_t s);
 int wide_newton_lds_bytes(int NB);
-hipError_t launch_loglik_eval(const EvalArgs& a, int family, int n_chunks, hipStream_t s);
+// routes on the row extras; each kernel is handed the slice of EvalArgsWgt it takes
+hipError_t launch_loglik_eval(const EvalArgsWgt& a, int family, int n_chunks, hipStream_t s);
 hipError_t launch_loglik_reduce(const double* partial, const int32_t* pcb, int K, int B,
                                 double* out, hipStream_t s);
-// weighted evaluation (eval_pass_wgt.hip); a.row_weight must be set
-hipError_t launch_loglik_eval_wgt(const EvalArgsWgt& a, int family, int n_chunks, hipStream_t s);
 int eval_slot_bytes(int p, int n_extras = 0);  // + 256 B per row extra behind y
 // per-wave fp64 pass (irls_wave_impl.hpp): P <= 128
 hipError_t launch_irls_wave(const PassArgsWgt& a, int NT, bool standardize, int family,
@@ -591,30 +604,20 @@ hipError_t launch_fit_init(const int64_t* offsets_dev, int K, int P, int start_p
 hipError_t launch_level_reset(int K, int P, int start_phase, int32_t* phase, int32_t* status,
                               double* ll_prev, int32_t* backtracks, double* theta,
                               int32_t* counters, hipStream_t s, const double* theta0 = nullptr);
-// Poisson start point (aux_kernels.hip): per partition one fixed-order pass
-// over y; theta0[k] = log(mean y) (intercept) or 0, written to theta[k][0]; a
-// negative or non-finite y ends the partition NONFINITE, sum y = 0 SINGULAR
-// (phase PHASE_DONE, outputs left zeroed by fit_init).  With eta_offset the
-// same pass sums exp(o): theta0[k] = log(sum y / sum exp(o)), and a non-finite
-// o or sum exp(o) ends the partition NONFINITE too
-hipError_t launch_poisson_start(const double* y, const int64_t* offsets_dev, int K, int P,
-                                int intercept, double* theta, double* theta0, int32_t* phase,
-                                int32_t* status, hipStream_t s,
-                                const double* eta_offset = nullptr);
-// Pre-pass of a weighted fit (aux_kernels.hip), after fit_init: one fixed-order
-// pass per partition over the prior weights omega.  A negative or non-finite
-// omega ends the partition NONFINITE, sum omega = 0 SINGULAR (phase
+// Pre-pass of a fit (aux_kernels.hip), after fit_init, for a family with a
+// device start (Poisson) or a fit with prior weights omega: per partition one
+// fixed-order pass over y, eta_offset and row_weight (either may be null:
+// o = 0, omega = 1).  A negative or non-finite y, o or omega ends the
+// partition NONFINITE, sum omega = 0 or (Poisson) sum omega y = 0 SINGULAR, a
+// sum omega exp(o) that is not finite and positive NONFINITE (phase
 // PHASE_DONE, outputs left zeroed by fit_init); nothing per row is stored.
-// Logistic: statuses only, the start stays theta = 0
-hipError_t launch_weight_check(const double* row_weight, const int64_t* offsets_dev, int K,
-                               int32_t* phase, int32_t* status, hipStream_t s);
-// Poisson: the weighted start point, theta0[k] = log(sum omega y / sum omega
-// exp(o)) with an intercept (o = 0 without an offset); the checks of
-// launch_poisson_start too, and sum omega y = 0 ends the partition SINGULAR
-hipError_t launch_poisson_start_wgt(const double* y, const double* eta_offset,
-                                    const double* row_weight, const int64_t* offsets_dev, int K,
-                                    int P, int intercept, double* theta, double* theta0,
-                                    int32_t* phase, int32_t* status, hipStream_t s);
+// Poisson: theta0[k] = log(sum omega y / sum omega exp(o)) with an intercept,
+// else 0, written to theta[k][0] too.  Logistic: statuses only (the weight
+// check); theta and theta0 are not touched.  A no-op for any other fit
+hipError_t launch_fit_prepass(int family, const double* y, const double* eta_offset,
+                              const double* row_weight, const int64_t* offsets_dev, int K, int P,
+                              int intercept, double* theta, double* theta0, int32_t* phase,
+                              int32_t* status, hipStream_t s);
 hipError_t launch_polish_mark(int K, int32_t* phase, const int32_t* status, int32_t* counters,
                               hipStream_t s);
 // theta_rec[k] = theta[k] for the partitions in phase `ph` (before a pass

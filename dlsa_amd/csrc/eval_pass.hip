@@ -14,20 +14,18 @@ namespace dlsa {
 
 int eval_slot_bytes(int p, int n_extras) { return eval_slot_bytes_impl(p, n_extras); }
 
-hipError_t launch_loglik_eval(const EvalArgs& a, int family, int n_chunks, hipStream_t s) {
-  const size_t lds = eval_lds_bytes(a);
+// Checks the family's rules and routes on the row-extras mask, like
+// launch_irls_coop; the weighted instantiations are eval_pass_wgt.hip's.
+hipError_t launch_loglik_eval(const EvalArgsWgt& a, int family, int n_chunks, hipStream_t s) {
   const FamilyRules rules = family_rules(family);
   if (a.eta_offset && !rules.offset) return hipErrorInvalidValue;
-  // the family whose log-likelihood has a constant term has its own kernel
-  auto kern = !rules.sums_ll_const ? loglik_eval_kernel<FAMILY_LOGISTIC>
-              : a.eta_offset       ? loglik_eval_kernel<FAMILY_POISSON, EX_OFS>
-                                   : loglik_eval_kernel<FAMILY_POISSON>;
-  {
-    hipError_t e = ensure_max_lds((const void*)kern, 160 * 1024);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(n_chunks), dim3(256), lds, s, a);
-  return hipGetLastError();
+  if (a.row_weight && !rules.weights) return hipErrorInvalidValue;
+  const int ex = pass_extras(a);
+  if (ex & EX_WGT) return launch_eval_unit_wgt(a, family, n_chunks, s);
+  if (rules.sums_ll_const)  // the family whose log-likelihood has a constant term: its own kernel
+    return ex & EX_OFS ? launch_eval_kernel<FAMILY_POISSON, EX_OFS>(a, n_chunks, s)
+                       : launch_eval_kernel<FAMILY_POISSON, EX_NONE>(a, n_chunks, s);
+  return launch_eval_kernel<FAMILY_LOGISTIC, EX_NONE>(a, n_chunks, s);
 }
 
 // ll[k, b] = sum of the chunk partials of partition k (fixed order)

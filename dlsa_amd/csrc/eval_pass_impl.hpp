@@ -194,4 +194,17 @@ __global__ __launch_bounds__(256) void loglik_eval_kernel(const typename eval_ar
   }
 }
 
+// One launch of the <FAM, EX> kernel on its slice of the arguments.
+template <int FAM, int EX>
+inline hipError_t launch_eval_kernel(const EvalArgsWgt& a, int n_chunks, hipStream_t s) {
+  auto kern = loglik_eval_kernel<FAM, EX>;
+  hipError_t e = ensure_max_lds((const void*)kern, 160 * 1024);
+  if (e != hipSuccess) return e;
+  const typename eval_args_of<EX>::type& slice = a;
+  hipLaunchKernelGGL(kern, dim3(n_chunks), dim3(256), eval_lds_bytes(a), s, slice);
+  return hipGetLastError();
+}
+// the unit that holds the weighted instantiations (eval_pass_wgt.hip)
+hipError_t launch_eval_unit_wgt(const EvalArgsWgt& a, int family, int n_chunks, hipStream_t s);
+
 }  // namespace dlsa

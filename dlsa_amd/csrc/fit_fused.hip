@@ -64,7 +64,6 @@ struct FusedFit {
 };
 
 void FusedFit::set_pass_args(const Plan& pl, const Workspace& ws, const Layout& L) {
-  const int64_t n_total = f.offsets[K];
   memset(&pa, 0, sizeof(pa));
   pa.X = f.X;
   pa.y = f.y;
@@ -79,16 +78,10 @@ void FusedFit::set_pass_args(const Plan& pl, const Workspace& ws, const Layout& 
   pa.slab_g = (double*)ws.at(L.off_slabg);
   pa.slab_ll = (double*)ws.at(L.off_slabll);
   pa.slab_llc = sa.slab_llc;
-  if (n_total > 0) {
-    const uintptr_t xend = (uintptr_t)(f.X + n_total * (int64_t)f.p);
-    pa.x_last16 = ((xend + 15) & ~(uintptr_t)15) - 16;
-    pa.y_last4 = (uintptr_t)(f.y + n_total) - 4;
-    if (f.eta_offset) pa.o_last4 = (uintptr_t)(f.eta_offset + n_total) - 4;
-    if (f.row_weight) pa.w_last4 = (uintptr_t)(f.row_weight + n_total) - 4;
-  }
   pa.eta_offset = f.eta_offset;
   pa.row_weight = f.row_weight;
   pa.p = f.p;
+  set_stream_bounds(pa, f.offsets[K]);
   pa.P = P;
   pa.intercept = f.fit_intercept ? 1 : 0;
   pa.waves = f.start.opt.exact_waves;
@@ -272,19 +265,12 @@ int FusedFit::run() {
   const int start_phase =
       (opt.hessian_mode == DLSA_HESSIAN_FP64 || !rules.iterates) ? PHASE_F64 : PHASE_F32;
   DLSA_HIP_TRY(fit_init(sa, d_offsets, K, start_phase, stream));
-  if (rules.device_start && f.row_weight)  // Poisson, weighted: start point and weight check
-    DLSA_HIP_TRY(launch_poisson_start_wgt(f.y, f.eta_offset, f.row_weight, d_offsets, K, P,
-                                          f.fit_intercept ? 1 : 0, sa.theta,
-                                          const_cast<double*>(sa.theta0), sa.phase, sa.status,
-                                          stream));
-  else if (rules.device_start)  // Poisson: the start point; ends the partitions that have no MLE
-    DLSA_HIP_TRY(launch_poisson_start(f.y, d_offsets, K, P, f.fit_intercept ? 1 : 0, sa.theta,
-                                      const_cast<double*>(sa.theta0), sa.phase, sa.status, stream,
-                                      f.eta_offset));
-  else if (f.row_weight)  // logistic, weighted: the weight check (statuses only)
-    DLSA_HIP_TRY(launch_weight_check(f.row_weight, d_offsets, K, sa.phase, sa.status, stream));
-  // the pre-pass may have ended partitions
+  // the start point of a family that has one and the weight check; may end partitions
   const bool pre_pass = rules.device_start || f.row_weight != nullptr;
+  if (pre_pass)
+    DLSA_HIP_TRY(launch_fit_prepass(family, f.y, f.eta_offset, f.row_weight, d_offsets, K, P,
+                                    f.fit_intercept ? 1 : 0, sa.theta,
+                                    const_cast<double*>(sa.theta0), sa.phase, sa.status, stream));
   int n_running[kRunPhases] = {0, 0, 0};
   for (int k = 0; k < K; ++k)
     if (offsets[k + 1] > offsets[k]) n_running[start_phase]++;

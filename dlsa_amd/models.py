@@ -279,53 +279,112 @@ class BatchedFit:
         return {_hip.STATUS_NAMES.get(int(v), str(v)): int((s == v).sum()) for v in np.unique(s)}
 
 
-def _check_eta_offset(X, eta_offset, exposure):
-    """The argument checks of a per-row offset, before anything touches the
-    GPU: one of ``eta_offset`` / ``exposure`` at most, n entries, and an
-    exposure that is finite and > 0 (its log is the offset)."""
-    if eta_offset is not None and exposure is not None:
-        raise ValueError("give eta_offset or exposure (eta_offset = log exposure), not both")
-    v = eta_offset if eta_offset is not None else exposure
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+
+
+def _size(v):
+    is_t = torch is not None and isinstance(v, torch.Tensor)
+    return int(v.numel()) if is_t else int(np.size(v))
+
+
+def _check_row_extra(name, v, n, pred=None, must=None):
+    """The argument check of a per-row extra ``v`` (None: not given), before
+    anything touches the GPU: n entries, and with ``pred`` every one finite
+    and satisfying it (``must``: the ValueError's text)."""
     if v is None:
         return
-    n = int(X.shape[0]) if hasattr(X, "shape") else int(np.shape(X)[0])
-    is_t = torch is not None and isinstance(v, torch.Tensor)
-    if (int(v.numel()) if is_t else int(np.size(v))) != n:
-        raise ValueError("eta_offset / exposure must have n entries (one per row of X)")
-    if exposure is not None:
-        if is_t:
-            ok = bool((torch.isfinite(v) & (v > 0)).all())
-        else:
-            a = np.asarray(v, dtype=np.float64)
-            ok = bool(np.isfinite(a).all() and (a > 0).all())
-        if not ok:
-            raise ValueError("exposure must be finite and > 0 (drop the rows with none)")
+    if _size(v) != n:
+        raise ValueError(f"{name} must have n entries (one per row of X)")
+    if pred is not None:
+        is_t = torch is not None and isinstance(v, torch.Tensor)
+        a = v if is_t else np.asarray(v, dtype=np.float64)
+        if not bool(((torch if is_t else np).isfinite(a) & pred(a)).all()):
+            raise ValueError(must)
 
 
-def _check_sample_weight(X, sample_weight):
-    """The argument checks of per-row prior weights, before anything touches
-    the GPU: n entries, every one finite and >= 0."""
-    if sample_weight is None:
-        return
-    n = int(X.shape[0]) if hasattr(X, "shape") else int(np.shape(X)[0])
-    v = sample_weight
-    is_t = torch is not None and isinstance(v, torch.Tensor)
-    if (int(v.numel()) if is_t else int(np.size(v))) != n:
-        raise ValueError("sample_weight must have n entries (one per row of X)")
-    if is_t:
-        ok = bool((torch.isfinite(v) & (v >= 0)).all())
-    else:
-        a = np.asarray(v, dtype=np.float64)
-        ok = bool(np.isfinite(a).all() and (a >= 0).all())
-    if not ok:
-        raise ValueError("sample_weight must be finite and >= 0")
+def _check_row_extras(X, with_offset, eta_offset, exposure, sample_weight):
+    """The checks of a family's offset and weight arguments: one of
+    ``eta_offset`` / ``exposure`` at most (its log is the offset, so an
+    exposure is finite and > 0), weights finite and >= 0."""
+    n = _shape(X)[0]
+    if with_offset:
+        if eta_offset is not None and exposure is not None:
+            raise ValueError("give eta_offset or exposure (eta_offset = log exposure), not both")
+        _check_row_extra("eta_offset / exposure", eta_offset, n)
+        _check_row_extra("eta_offset / exposure", exposure, n, lambda a: a > 0,
+                         "exposure must be finite and > 0 (drop the rows with none)")
+    _check_row_extra("sample_weight", sample_weight, n, lambda a: a >= 0,
+                     "sample_weight must be finite and >= 0")
 
 
-def _dev_eta_offset(eta_offset, exposure, dev):
-    """[n] fp64 offset on the device (log exposure taken there), or None."""
-    if exposure is not None:
-        return torch.log(_dev_f64(exposure, dev).reshape(-1))
-    return _dev_f64(eta_offset, dev).reshape(-1) if eta_offset is not None else None
+def _entry_and_extras(entry, weighted_entry, with_offset, eta_offset, exposure, sample_weight,
+                      dev):
+    """The C-ABI symbol of a family's call and the device tensors it takes
+    between y and offsets (None: a null pointer): with ``with_offset``,
+    ``entry`` takes the [n] offset (log exposure taken on the device; null
+    when neither is given); with ``sample_weight`` the call is
+    ``weighted_entry``, which takes the weights behind that."""
+    extras = []
+    if with_offset:
+        od = None
+        if exposure is not None:
+            od = torch.log(_dev_f64(exposure, dev).reshape(-1))
+        elif eta_offset is not None:
+            od = _dev_f64(eta_offset, dev).reshape(-1)
+        extras.append(od)
+    if sample_weight is not None:
+        entry = weighted_entry
+        extras.append(_dev_f64(sample_weight, dev).reshape(-1))
+    return entry, extras
+
+
+def _check_rows(offsets, n, y):
+    """Host offsets [K+1] int64 of n rows, checked together with y's length."""
+    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if offs.ndim != 1 or offs.size < 2 or offs[0] != 0 or offs[-1] != n or \
+            np.any(np.diff(offs) < 0):
+        raise ValueError("offsets must be non-decreasing, start at 0 and end at n")
+    if _size(y) != n:
+        raise ValueError("y must have n entries")
+    return offs
+
+
+def _center_scale(center, scale, ncols, what, dev=None):
+    """center / scale: both or neither, ``ncols`` entries each (``what``: the
+    count in words).  With ``dev`` their [ncols] device copies (None, None
+    without them)."""
+    if center is None and scale is None:
+        return None, None
+    if center is None or scale is None or _size(center) != ncols or _size(scale) != ncols:
+        raise ValueError(f"center and scale must both be given, with {what} entries each")
+    if dev is None:
+        return None, None
+    return _dev_f64(center, dev).reshape(-1), _dev_f64(scale, dev).reshape(-1)
+
+
+def _dense_inputs(X, y, offsets, center, scale, device):
+    """Checked device copies of a dense layout, the dense counterpart of
+    ``_cat_inputs``: (device, X [n, p] fp64, y [n], host offsets [K+1] int64,
+    center, scale ([p] or None)).  Every check comes before the GPU is
+    touched."""
+    if len(_shape(X)) != 2:
+        raise ValueError("X must be 2-D [n, p]")
+    n, p = _shape(X)
+    offs = _check_rows(offsets, n, y)
+    _center_scale(center, scale, p, "p")
+    dev = _require_gpu(device)
+    return (dev, _dev_f64(X, dev), _dev_f64(y, dev).reshape(-1), offs,
+            *_center_scale(center, scale, p, "p", dev))
+
+
+def _alloc_outputs(K, P, dev):
+    """The six output tensors of a fit: theta, sig_inv, sig_inv_theta, loglik,
+    iters, status."""
+    f64 = dict(dtype=torch.float64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    return (torch.empty((K, P), **f64), torch.empty((K, P, P), **f64), torch.empty((K, P), **f64),
+            torch.empty((K,), **f64), torch.empty((K,), **i32), torch.empty((K,), **i32))
 
 
 def _glm_model_batched(entry, X, y, offsets, fit_intercept, center, scale, max_iter, tol,
@@ -339,42 +398,15 @@ def _glm_model_batched(entry, X, y, offsets, fit_intercept, center, scale, max_i
     With ``sample_weight`` the call is ``weighted_entry`` instead, which takes
     the weights after y (after ``eta_offset`` when ``with_offset``).
     Returns a BatchedFit."""
-    if with_offset:
-        _check_eta_offset(X, eta_offset, exposure)
-    _check_sample_weight(X, sample_weight)
-    dev = _require_gpu(device)
-    Xd = _dev_f64(X, dev)
-    yd = _dev_f64(y, dev).reshape(-1)
-    od = _dev_eta_offset(eta_offset, exposure, dev) if with_offset else None
-    extra = [_ptr(od)] if with_offset else []
-    if sample_weight is not None:
-        wd = _dev_f64(sample_weight, dev).reshape(-1)
-        entry = weighted_entry
-        extra.append(_ptr(wd))
-    if Xd.dim() != 2:
-        raise ValueError("X must be 2-D [n, p]")
-    n, p = Xd.shape
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    K = offs.size - 1
-    if K < 1 or offs[0] != 0 or offs[-1] != n or np.any(np.diff(offs) < 0):
-        raise ValueError("offsets must be non-decreasing, start at 0 and end at n")
-    if yd.numel() != n:
-        raise ValueError("y must have n entries")
+    _check_row_extras(X, with_offset, eta_offset, exposure, sample_weight)
+    dev, Xd, yd, offs, cd, sd = _dense_inputs(X, y, offsets, center, scale, device)
+    entry, extras = _entry_and_extras(entry, weighted_entry, with_offset, eta_offset, exposure,
+                                      sample_weight, dev)
+    p, K = Xd.shape[1], offs.size - 1
     P = p + (1 if fit_intercept else 0)
     if P > _hip.MAX_P:
         raise DlsaHipError(f"P = {P} > {_hip.MAX_P} is not supported")
-    cd = sd = None
-    if center is not None or scale is not None:
-        cd = _dev_f64(center, dev).reshape(-1)
-        sd = _dev_f64(scale, dev).reshape(-1)
-        if cd.numel() != p or sd.numel() != p:
-            raise ValueError("center/scale must have p entries")
-    theta = torch.empty((K, P), dtype=torch.float64, device=dev)
-    sig = torch.empty((K, P, P), dtype=torch.float64, device=dev)
-    sigt = torch.empty((K, P), dtype=torch.float64, device=dev)
-    ll = torch.empty((K,), dtype=torch.float64, device=dev)
-    iters = torch.empty((K,), dtype=torch.int32, device=dev)
-    status = torch.empty((K,), dtype=torch.int32, device=dev)
+    theta, sig, sigt, ll, iters, status = _alloc_outputs(K, P, dev)
 
     lib = _hip.load()
     opt = _hip.default_options()
@@ -396,7 +428,7 @@ def _glm_model_batched(entry, X, y, offsets, fit_intercept, center, scale, max_i
     opt.workspace = workspace.data_ptr()
     opt.workspace_bytes = workspace.numel()
     rc = getattr(lib, entry)(
-        _ptr(Xd), _ptr(yd), *extra, offs_p, K, p,
+        _ptr(Xd), _ptr(yd), *map(_ptr, extras), offs_p, K, p,
         int(bool(fit_intercept)), _ptr(cd), _ptr(sd),
         int(max_iter), float(tol), _ptr(theta), _ptr(sig), _ptr(sigt), _ptr(ll), _ptr(iters),
         _ptr(status), ctypes.byref(opt), _stream(dev))
@@ -532,10 +564,9 @@ def _cat_inputs(Xn, codes, y, offsets, levels, center, scale, dev):
     """Checked device copies of a categorical-code layout: (Xn [n, q] fp64,
     codes [n, F] uint8, y [n], host offsets [K+1] int64, host levels [F]
     int32, center, scale ([q] or None))."""
-    Xd = _dev_f64(Xn, dev)
-    if Xd.dim() != 2:
+    if len(_shape(Xn)) != 2:
         raise ValueError("Xn must be 2-D [n, q]")
-    n, q = Xd.shape
+    n, q = _shape(Xn)
     if isinstance(codes, torch.Tensor):
         cd8 = codes.to(device=dev, dtype=torch.uint8).contiguous()
     else:
@@ -545,18 +576,9 @@ def _cat_inputs(Xn, codes, y, offsets, levels, center, scale, dev):
     lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32).reshape(-1))
     if lv.size != cd8.shape[1]:
         raise ValueError("levels must have F entries")
-    yd = _dev_f64(y, dev).reshape(-1)
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    K = offs.size - 1
-    if K < 1 or offs[0] != 0 or offs[-1] != n or np.any(np.diff(offs) < 0) or yd.numel() != n:
-        raise ValueError("offsets must be non-decreasing, start at 0 and end at n; y has n rows")
-    cen = sca = None
-    if center is not None or scale is not None:
-        cen = _dev_f64(center, dev).reshape(-1)
-        sca = _dev_f64(scale, dev).reshape(-1)
-        if cen.numel() != q or sca.numel() != q:
-            raise ValueError("center/scale must have q entries (numeric columns)")
-    return Xd, cd8, yd, offs, lv, cen, sca
+    offs = _check_rows(offsets, n, y)
+    cen, sca = _center_scale(center, scale, q, "q (the numeric columns)", dev)
+    return _dev_f64(Xn, dev), cd8, _dev_f64(y, dev).reshape(-1), offs, lv, cen, sca
 
 
 def logistic_model_batched_categorical(Xn, codes, y, offsets, levels, fit_intercept=False,
@@ -583,12 +605,7 @@ def logistic_model_batched_categorical(Xn, codes, y, offsets, levels, fit_interc
                                                   dev)
     q, F, K = Xd.shape[1], cd8.shape[1], offs.size - 1
     P = int(bool(fit_intercept)) + q + int((lv - 1).sum())
-    theta = torch.empty((K, P), dtype=torch.float64, device=dev)
-    sig = torch.empty((K, P, P), dtype=torch.float64, device=dev)
-    sigt = torch.empty((K, P), dtype=torch.float64, device=dev)
-    ll = torch.empty((K,), dtype=torch.float64, device=dev)
-    iters = torch.empty((K,), dtype=torch.int32, device=dev)
-    status = torch.empty((K,), dtype=torch.int32, device=dev)
+    theta, sig, sigt, ll, iters, status = _alloc_outputs(K, P, dev)
     lib = _hip.load()
     opt = _hip.default_options()
     opt.record_timing = 1 if record_timing else 0
@@ -614,26 +631,13 @@ def ols_model_batched(X, y, offsets, fit_intercept=False, center=None, scale=Non
     partition theta_k = (X_k^T X_k)^-1 X_k^T y_k and Sig_inv_k = X_k^T X_k from
     one fused fp64 pass.  Returns a BatchedFit whose ``loglik`` field holds the
     residual sum of squares of each partition."""
-    dev = _require_gpu(device)
-    Xd = _dev_f64(X, dev)
-    yd = _dev_f64(y, dev).reshape(-1)
-    n, p = Xd.shape
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    K = offs.size - 1
-    if K < 1 or offs[0] != 0 or offs[-1] != n or np.any(np.diff(offs) < 0) or yd.numel() != n:
-        raise ValueError("offsets must be non-decreasing, start at 0 and end at n; y has n rows")
+    dev, Xd, yd, offs, cd, sd = _dense_inputs(X, y, offsets, center, scale, device)
+    p, K = Xd.shape[1], offs.size - 1
     P = p + (1 if fit_intercept else 0)
     if P > _hip.MAX_P:
         raise DlsaHipError(f"P = {P} > {_hip.MAX_P} is not supported")
-    cd = sd = None
-    if center is not None or scale is not None:
-        cd = _dev_f64(center, dev).reshape(-1)
-        sd = _dev_f64(scale, dev).reshape(-1)
-    theta = torch.empty((K, P), dtype=torch.float64, device=dev)
-    sig = torch.empty((K, P, P), dtype=torch.float64, device=dev)
-    sigt = torch.empty((K, P), dtype=torch.float64, device=dev)
-    rss = torch.empty((K,), dtype=torch.float64, device=dev)
-    status = torch.empty((K,), dtype=torch.int32, device=dev)
+    theta, sig, sigt, rss, iters, status = _alloc_outputs(K, P, dev)
+    iters.fill_(1)
     lib = _hip.load()
     opt = _hip.default_options()
     opt.rows_per_chunk = int(rows_per_chunk)
@@ -644,7 +648,6 @@ def ols_model_batched(X, y, offsets, fit_intercept=False, center=None, scale=Non
                                   _ptr(sig), _ptr(sigt), _ptr(rss), _ptr(status),
                                   ctypes.byref(opt), _stream(dev))
     _hip.check(rc, "dlsa_ols_fit_batched")
-    iters = torch.ones((K,), dtype=torch.int32, device=dev)
     return BatchedFit(theta, sig, sigt, rss, iters, status, offs, bool(fit_intercept),
                       _hip.last_fit_stats())
 
@@ -680,32 +683,16 @@ def _loglik_dense(entry, X, y, offsets, betas, fit_intercept, center, scale, dev
     ``*_loglik_batched_sum`` symbol, or with ``with_offset`` one that takes
     ``eta_offset`` after y; with ``sample_weight`` ``weighted_entry``, which
     takes the weights behind those) through ``_loglik_groups``."""
-    if with_offset:
-        _check_eta_offset(X, eta_offset, exposure)
-    _check_sample_weight(X, sample_weight)
-    dev = _require_gpu(device)
-    Xd = _dev_f64(X, dev)
-    yd = _dev_f64(y, dev).reshape(-1)
-    od = _dev_eta_offset(eta_offset, exposure, dev) if with_offset else None
-    extra = [_ptr(od)] if with_offset else []
-    if sample_weight is not None:
-        wd = _dev_f64(sample_weight, dev).reshape(-1)
-        entry = weighted_entry
-        extra.append(_ptr(wd))
-    n, p = Xd.shape
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    K = offs.size - 1
-    if K < 1 or offs[0] != 0 or offs[-1] != n or np.any(np.diff(offs) < 0) or yd.numel() != n:
-        raise ValueError("offsets must be non-decreasing, start at 0 and end at n; y has n rows")
-    cd = sd = None
-    if center is not None or scale is not None:
-        cd = _dev_f64(center, dev).reshape(-1)
-        sd = _dev_f64(scale, dev).reshape(-1)
+    _check_row_extras(X, with_offset, eta_offset, exposure, sample_weight)
+    dev, Xd, yd, offs, cd, sd = _dense_inputs(X, y, offsets, center, scale, device)
+    entry, extras = _entry_and_extras(entry, weighted_entry, with_offset, eta_offset, exposure,
+                                      sample_weight, dev)
+    p, K = Xd.shape[1], offs.size - 1
     fn = getattr(_hip.load(), entry)
 
     def call(bd, g, out, total):
-        rc = fn(_ptr(Xd), _ptr(yd), *extra,
-                offs.ctypes.data_as(ctypes.c_void_p), K, p, int(bool(fit_intercept)), _ptr(cd), _ptr(sd), _ptr(bd), g, _ptr(out), _ptr(total),
+        rc = fn(_ptr(Xd), _ptr(yd), *map(_ptr, extras), offs.ctypes.data_as(ctypes.c_void_p), K, p,
+                int(bool(fit_intercept)), _ptr(cd), _ptr(sd), _ptr(bd), g, _ptr(out), _ptr(total),
                 _stream(dev))
         _hip.check(rc, entry)
 
@@ -804,6 +791,40 @@ def _describe_row(data_info, col, row):
     return float(data_info[col][row])
 
 
+def _center_scale_from_info(data_info, cols, numeric):
+    """center / scale [len(cols)] of models.py:99-101: the mean and stddev of
+    ``data_info`` on the numeric columns, 0 and 1 on the others; (None, None)
+    without ``data_info`` or columns."""
+    if len(data_info) == 0 or len(cols) == 0:
+        return None, None
+    center = np.zeros(len(cols))
+    scale = np.ones(len(cols))
+    for j, c in enumerate(cols):
+        if c in numeric:
+            center[j] = _describe_row(data_info, c, 1)
+            scale[j] = _describe_row(data_info, c, 2)
+    return center, scale
+
+
+def _result_frame(icpt, cols, fit=None):
+    """The reference's output frame ``par_id | coef | Sig_invMcoef | <Sig_inv
+    columns>`` of partition 0 of ``fit``; without one its all-zero frame
+    (models.py:84-91)."""
+    import pandas as pd
+
+    names = ["coef", "Sig_invMcoef"] + icpt + cols
+    P = len(icpt) + len(cols)
+    if fit is None:
+        return pd.DataFrame(0, index=np.arange(P), columns=["par_id"] + names)
+    out = pd.DataFrame(np.column_stack([fit.theta[0].cpu().numpy(),
+                                        fit.sig_inv_theta[0].cpu().numpy(),
+                                        fit.sig_inv[0].cpu().numpy()]), columns=pd.Index(names))
+    out.insert(0, "par_id", np.arange(P))
+    if out.isna().values.any():
+        warnings.warn("NAs appear in the final output")
+    return out
+
+
 def _design(sample_df, Y_name, dummy_info, dummy_factors_baseline):
     """Host-side design matrix of one partition, models.py:56-104.  Returns
     (x_train DataFrame, usecols_x0 numeric columns, usecols_x all columns,
@@ -834,8 +855,6 @@ def _logistic_model_codes(sample_df, Y_name, fit_intercept, dummy_info, dummy_fa
     dummy matrix).  None when the design exceeds the kernel's limits (F <= 16
     factors, intercept + numeric <= 16, P <= 192): the caller then builds the
     dense design."""
-    import pandas as pd
-
     icpt = ["intercept"] if fit_intercept else []
     enc = encode_categorical(sample_df, Y_name, dummy_info, dummy_factors_baseline)
     q, F = enc["Xn"].shape[1], enc["codes"].shape[1]
@@ -847,25 +866,13 @@ def _logistic_model_codes(sample_df, Y_name, fit_intercept, dummy_info, dummy_fa
         absent = [c for c, m in zip(cols[q:], enc["counts"]) if m == 0]
         warnings.warn("Dummies:" + str(set(absent)) + "missing in this data chunk "
                       + str((len(sample_df), len(cols))) + "Skip modeling this part of data.")
-        return pd.DataFrame(0, index=np.arange(P),
-                            columns=["par_id", "coef", "Sig_invMcoef"] + icpt + cols)
-    center = scale = None
-    if len(data_info) > 0 and q > 0:
-        center = np.array([_describe_row(data_info, c, 1) for c in enc["numeric"]])
-        scale = np.array([_describe_row(data_info, c, 2) for c in enc["numeric"]])
+        return _result_frame(icpt, cols)
+    center, scale = _center_scale_from_info(data_info, enc["numeric"], enc["numeric"])
     y = np.asarray(sample_df[Y_name], dtype=np.float64)
     fit = logistic_model_batched_categorical(enc["Xn"], enc["codes"], y, np.array([0, y.size]),
                                              enc["levels"], fit_intercept=fit_intercept,
                                              center=center, scale=scale)
-    coef = fit.theta[0].cpu().numpy()
-    sig = fit.sig_inv[0].cpu().numpy()
-    sigt = fit.sig_inv_theta[0].cpu().numpy()
-    out = pd.DataFrame(np.column_stack([coef, sigt, sig]),
-                       columns=pd.Index(["coef", "Sig_invMcoef"] + icpt + cols))
-    out.insert(0, "par_id", np.arange(P))
-    if out.isna().values.any():
-        warnings.warn("NAs appear in the final output")
-    return out
+    return _result_frame(icpt, cols, fit)
 
 
 def logistic_model(sample_df, Y_name, fit_intercept=False, dummy_info=[], dummy_factors_baseline=[],
@@ -878,8 +885,6 @@ def logistic_model(sample_df, Y_name, fit_intercept=False, dummy_info=[], dummy_
     all-zero frame (models.py:84-91).  The estimate is the converged MLE (the
     reference stops sklearn at its default tol=1e-4); the fit runs on the GPU.
     """
-    import pandas as pd
-
     icpt = ["intercept"] if fit_intercept else []
     if len(dummy_info) > 0:
         out = _logistic_model_codes(sample_df, Y_name, fit_intercept, dummy_info,
@@ -891,31 +896,14 @@ def logistic_model(sample_df, Y_name, fit_intercept=False, dummy_info=[], dummy_
         warnings.warn("Dummies:" + str(set(cols) - set(x_train.columns))
                       + "missing in this data chunk " + str(x_train.shape)
                       + "Skip modeling this part of data.")
-        return pd.DataFrame(0, index=np.arange(len(icpt + cols)),
-                            columns=["par_id", "coef", "Sig_invMcoef"] + icpt + cols)
+        return _result_frame(icpt, cols)
     x_train = x_train.reindex(columns=cols)
     X = np.ascontiguousarray(x_train.to_numpy(dtype=np.float64))
     y = np.asarray(sample_df[Y_name], dtype=np.float64)
-    center = scale = None
-    if len(data_info) > 0:
-        center = np.zeros(len(cols))
-        scale = np.ones(len(cols))
-        for j, c in enumerate(cols):
-            if c in numeric:
-                center[j] = _describe_row(data_info, c, 1)
-                scale[j] = _describe_row(data_info, c, 2)
+    center, scale = _center_scale_from_info(data_info, cols, numeric)
     fit = logistic_model_batched(X, y, np.array([0, X.shape[0]]), fit_intercept=fit_intercept,
                                  center=center, scale=scale)
-    coef = fit.theta[0].cpu().numpy()
-    sig = fit.sig_inv[0].cpu().numpy()
-    sigt = fit.sig_inv_theta[0].cpu().numpy()
-    P = coef.size
-    out = pd.DataFrame(np.column_stack([coef, sigt, sig]),
-                       columns=pd.Index(["coef", "Sig_invMcoef"] + icpt + cols))
-    out.insert(0, "par_id", np.arange(P))
-    if out.isna().values.any():
-        warnings.warn("NAs appear in the final output")
-    return out
+    return _result_frame(icpt, cols, fit)
 
 
 def logistic_model_eval(sample_df, Y_name, par, fit_intercept=False, dummy_info=[],
@@ -943,10 +931,7 @@ def logistic_model_eval(sample_df, Y_name, par, fit_intercept=False, dummy_info=
                 absent = [c for c, m in zip(enc["cols"][q:], enc["counts"]) if m == 0]
                 warnings.warn("Dummies:" + str(set(absent)) + "missing in this data chunk "
                               + str((len(sample_df), len(enc["cols"]))))
-            center = scale = None
-            if len(data_info) > 0 and q > 0:
-                center = np.array([_describe_row(data_info, c, 1) for c in enc["numeric"]])
-                scale = np.array([_describe_row(data_info, c, 2) for c in enc["numeric"]])
+            center, scale = _center_scale_from_info(data_info, enc["numeric"], enc["numeric"])
             y = np.asarray(sample_df[Y_name], dtype=np.float64)
             ll = logistic_loglik_batched_categorical(
                 enc["Xn"], enc["codes"], y, np.array([0, y.size]), enc["levels"], betas,
@@ -959,14 +944,7 @@ def logistic_model_eval(sample_df, Y_name, par, fit_intercept=False, dummy_info=
     x_train = x_train.reindex(columns=cols, fill_value=0)
     X = np.ascontiguousarray(x_train.to_numpy(dtype=np.float64))
     y = np.asarray(sample_df[Y_name], dtype=np.float64)
-    center = scale = None
-    if len(data_info) > 0:
-        center = np.zeros(len(cols))
-        scale = np.ones(len(cols))
-        for j, c in enumerate(cols):
-            if c in numeric:
-                center[j] = _describe_row(data_info, c, 1)
-                scale[j] = _describe_row(data_info, c, 2)
+    center, scale = _center_scale_from_info(data_info, cols, numeric)
     ll = logistic_loglik_batched(X, y, np.array([0, X.shape[0]]), betas,
                                  fit_intercept=fit_intercept, center=center, scale=scale)
     return pd.DataFrame(ll.cpu().numpy(), columns=list(par.columns))

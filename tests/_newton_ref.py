@@ -35,7 +35,7 @@ import functools
 
 import numpy as np
 
-import _poisson_ref as R
+import _glm_ref as G
 import oracle as O
 
 PHASE_F32, PHASE_F32X, PHASE_F64 = 0, 1, 2
@@ -66,7 +66,7 @@ class Design:
 
     def __init__(self, X, fit_intercept=False, center=None, scale=None, path="fused"):
         X = np.asarray(X, dtype=np.float64)
-        self.Z = R.design(X, fit_intercept, center, scale)  # the reference's design
+        self.Z = G.design(X, fit_intercept, center, scale)  # the reference's design
         if center is None:
             xs = X
         else:
@@ -179,7 +179,7 @@ def _run(D, y, family, fit_intercept, mode, max_iter, tol, switch_tol, path, def
     P = D.P
     theta = np.zeros(P)
     if family == "poisson" and fit_intercept:
-        theta[0] = np.log(y.sum() / y.size)  # poisson_start_kernel
+        theta[0] = np.log(y.sum() / y.size)  # fit_prepass_kernel
     start = theta.copy()
     phase = PHASE_F64 if mode == "fp64" else PHASE_F32
     escalate_to = PHASE_F32X if (mode == "mixed" and path == "fused") else PHASE_F64
@@ -474,7 +474,7 @@ def case_data(fam, p, fi, std, wide=False, seed=0):
     b = np.zeros(p)
     b[:max(1, int(0.4 * p))] = poisson_beta(p)
     if fam == "poisson" and not std:
-        X, y = R.simulate(n, p, seed, fit_intercept=fi, theta_true=b)
+        X, y = G.simulate(n, p, seed, fit_intercept=fi, theta_true=b)
     else:
         X, y = O.simulate_counter(n, p, seed)
         X = np.ascontiguousarray(X)
@@ -532,11 +532,11 @@ def halving_data():
     """test_gpu_poisson.test_overshoot[False]: mean y ~ 39, start theta = 0.
     The 8000 rows are cut into K = 4 partitions of 2000 (<= 2048, so no
     warm-start level; every one of them overshoots the same way).
-    test_cpu_newton_ref also pins the emulator against _poisson_ref.fit on all
+    test_cpu_newton_ref also pins the emulator against _glm_ref.fit on all
     8000 rows as one partition."""
     th = np.zeros(10)
     th[0] = 1.2
-    X, y = R.simulate(HALVING_N, 10, seed=11, shift0=3.0, theta_true=th)
+    X, y = G.simulate(HALVING_N, 10, seed=11, shift0=3.0, theta_true=th)
     off = np.arange(5, dtype=np.int64) * 2000
     return X, y, off
 
@@ -561,6 +561,6 @@ MANY_SAMPLE = (0, 1, 77, 255, 256, 257, 298, 299)
 
 @functools.lru_cache(maxsize=None)
 def many_data():
-    X, y = R.simulate(MANY_K * MANY_N, MANY_P, seed=17, fit_intercept=True)
+    X, y = G.simulate(MANY_K * MANY_N, MANY_P, seed=17, fit_intercept=True)
     off = np.arange(MANY_K + 1, dtype=np.int64) * MANY_N
     return X, y, off

@@ -408,8 +408,7 @@ def problem(c):
     """Data, expected statuses and yardstick of a case, computed once per
     process: a dict with X, y, (eta_offset, center, scale, codes), `status`
     [K] and `ref`: partition -> dict(theta, sig_inv, sig_inv_theta, loglik)."""
-    import _poisson_offset_ref as RO
-    import _poisson_ref as R
+    import _glm_ref as G
     import oracle as O
 
     off = c.offsets
@@ -432,12 +431,12 @@ def problem(c):
         y = X @ rs.randn(c.p) + 0.3 + 0.1 * rs.randn(n)
     elif c.data == "poisson":  # the cached cases (and fits) of the Poisson test modules
         if ofs:
-            X, y, o, _, pref = RO.case(c.p, c.fi, c.sizes)
+            X, y, o, _, pref = G.case_offset(c.p, c.fi, c.sizes)
             d["eta_offset"] = o
         else:
-            X, y, _, pref = R.case(c.p, c.fi, c.sizes)
+            X, y, _, pref = G.case(c.p, c.fi, c.sizes)
     elif c.data == "poisson_bad":
-        X, y = R.simulate(n, c.p, seed=3)
+        X, y = G.simulate(n, c.p, seed=3)
         y = y.copy()
         y[2000 + 777] = -1.0
         y[4000:6000] = 0.0
@@ -445,13 +444,13 @@ def problem(c):
     elif c.data == "poisson_overflow":
         th = np.zeros(c.p)
         th[0] = 2.3
-        X, y = R.simulate(n, c.p, seed=13, shift0=3.0, theta_true=th)
+        X, y = G.simulate(n, c.p, seed=13, shift0=3.0, theta_true=th)
     elif c.data == "poisson_dirty":
         # the overshoot design of test_gpu_poisson.test_overshoot (no intercept,
         # mean y ~ 39: the step from theta = 0 is halved), one all-zero-y partition
         th = np.zeros(c.p)
         th[0] = 1.2
-        X, y = R.simulate(n, c.p, seed=11, shift0=3.0, theta_true=th)
+        X, y = G.simulate(n, c.p, seed=11, shift0=3.0, theta_true=th)
         y = y.copy()
         y[int(off[4]):int(off[5])] = 0.0
         status[4] = STATUS_SINGULAR
@@ -500,7 +499,7 @@ def problem(c):
                                                        "loglik")}
         elif c.entry == "logistic":
             o = O.logistic_fit(Xref[a:b], y[a:b], fit_intercept=c.fi, **std)
-            Z = R.design(Xref[a:b], c.fi, d["center"], d["scale"])
+            Z = G.design(Xref[a:b], c.fi, d["center"], d["scale"])
             ll = float(O.logistic_loglik(Z, y[a:b], o["coef"])[0])
             ref[k] = dict(theta=o["coef"], sig_inv=o["Sig_inv"], sig_inv_theta=o["Sig_invMcoef"],
                           loglik=ll)
@@ -512,14 +511,14 @@ def problem(c):
                           loglik=ll)
         elif c.entry == "ols":
             o = O.ols_fit(X[a:b], y[a:b], fit_intercept=c.fi)
-            Z = R.design(X[a:b], c.fi)
+            Z = G.design(X[a:b], c.fi)
             rss = float(((y[a:b] - Z @ o["coef"]) ** 2).sum())
             ref[k] = dict(theta=o["coef"], sig_inv=o["Sig_inv"], sig_inv_theta=o["Sig_invMcoef"],
                           loglik=rss)
         elif ofs:
-            ref[k] = RO.fit(X[a:b], y[a:b], d["eta_offset"][a:b], fit_intercept=c.fi)
+            ref[k] = G.fit("poisson", X[a:b], y[a:b], o=d["eta_offset"][a:b], fit_intercept=c.fi)
         else:
-            ref[k] = R.fit(X[a:b], y[a:b], fit_intercept=c.fi)
+            ref[k] = G.fit("poisson", X[a:b], y[a:b], fit_intercept=c.fi)
     d["ref"] = ref
     return d
 

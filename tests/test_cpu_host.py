@@ -91,6 +91,40 @@ def test_fit_fails_loudly_without_gpu():
         logistic_model_batched(np.zeros((4, 2)), np.zeros(4), [0, 4])
 
 
+@pytest.mark.parametrize("bad", ["1-D X", "offsets", "center without scale", "y length"])
+def test_dense_inputs_checked_before_the_gpu(bad, monkeypatch):
+    """Every public dense entry of models.py refuses a malformed layout with a
+    ValueError before anything touches the GPU: _require_gpu is replaced by a
+    function that fails the test."""
+    from dlsa_amd import models as M
+
+    def no_gpu(device=None):
+        raise AssertionError("the GPU was touched before the input checks")
+
+    monkeypatch.setattr(M, "_require_gpu", no_gpu)
+    n, p = 40, 3
+    X, y, off, kw = np.zeros((n, p)), np.zeros(n), np.array([0, 25, n]), {}
+    if bad == "1-D X":
+        X = np.zeros(n)
+    elif bad == "offsets":
+        off = np.array([0, 25, n - 1])
+    elif bad == "center without scale":
+        kw = {"center": np.zeros(p)}
+    else:
+        y = np.zeros(n - 1)
+    betas = np.zeros((1, p))
+    fits = [M.logistic_model_batched, M.logistic_model_batched_weighted, M.poisson_model_batched,
+            M.poisson_model_batched_offset, M.poisson_model_batched_weighted, M.ols_model_batched]
+    evals = [M.logistic_loglik_batched, M.poisson_loglik_batched, M.poisson_loglik_batched_offset,
+             M.poisson_loglik_batched_weighted]
+    for fn in fits:
+        with pytest.raises(ValueError):
+            fn(X, y, off, **kw)
+    for fn in evals:
+        with pytest.raises(ValueError):
+            fn(X, y, off, betas, **kw)
+
+
 @pytest.mark.parametrize("typ", ["lar", "lasso"])
 def test_native_lars_config1_golden(golden_dir, typ):
     from dlsa_amd.lsa import lars_lsa

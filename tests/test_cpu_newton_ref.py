@@ -3,7 +3,7 @@ conditions the cases of tests/test_gpu_newton_steps.py must meet for its
 tolerance to mean something.  No GPU, plain numpy.
 
 * In "fp64" mode the emulator run to convergence is the existing references:
-  _poisson_ref.fit (theta and the number of halvings) and the oracle's
+  _glm_ref.fit (theta and the number of halvings) and the oracle's
   logistic fit.
 * For every GPU case, partition and checked iteration m: the modelled fp32
   accumulation noise of a correct approximate pass is at most 0.01 D_m, D_m
@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 import _newton_ref as N
-import _poisson_ref as R
+import _glm_ref as G
 import oracle as O
 
 MARGIN = 10.0
@@ -46,7 +46,7 @@ def _weakest(tr):
 
 def test_fp64_mode_is_poisson_ref_on_the_overshoot_case():
     X, y, _ = N.halving_data()
-    ref = R.fit(X, y)
+    ref = G.fit("poisson", X, y)
     tr = N.trajectory(X, y, "poisson", mode="fp64", max_iter=200, tol=1e-12)
     halvings = sum(r["halved"] for r in tr["rec"])
     print("halvings", halvings, ref["halvings"], "iters", tr["iters"], ref["iters"],
@@ -61,7 +61,7 @@ def test_fp64_mode_is_poisson_ref_on_the_overshoot_case():
 def test_fp64_mode_is_poisson_ref_on_a_plain_shape():
     X, y, off, _, _ = N.case_data("poisson", 64, True, False)
     a, b = off[1], off[2]
-    ref = R.fit(X[a:b], y[a:b], fit_intercept=True)
+    ref = G.fit("poisson", X[a:b], y[a:b], fit_intercept=True)
     tr = N.trajectory(X[a:b], y[a:b], "poisson", fit_intercept=True, mode="fp64", max_iter=200,
                       tol=1e-12)
     assert tr["status"] == "ok" and ref["halvings"] == 0
@@ -248,4 +248,4 @@ def test_many_partition_case_conditions():
         assert _min_margin(tr) >= MARGIN, _weakest(tr)
         ex = N.trajectory(D, y[a:b], "poisson", True, mode="fp64", max_iter=2)
         assert _min_margin(ex) >= MARGIN, _weakest(ex)
-        assert R.fit(X[a:b], y[a:b], fit_intercept=True)["halvings"] == 0
+        assert G.fit("poisson", X[a:b], y[a:b], fit_intercept=True)["halvings"] == 0

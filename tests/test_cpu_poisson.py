@@ -1,4 +1,4 @@
-"""Poisson family, CPU side: the numpy yardstick of tests/_poisson_ref.py
+"""Poisson family, CPU side: the numpy yardstick of tests/_glm_ref.py
 against scikit-learn, and the C-ABI declarations of the new entry points."""
 
 import ctypes
@@ -8,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-import _poisson_ref as R
+import _glm_ref as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -22,25 +22,25 @@ def _rel(a, b):
 @pytest.mark.parametrize("p,fi", [(16, False), (33, False), (64, True)])
 def test_reference_vs_sklearn(p, fi):
     lm = pytest.importorskip("sklearn.linear_model")
-    X, y = R.simulate(1500, p, seed=7, fit_intercept=fi)
-    ref = R.fit(X, y, fit_intercept=fi)
+    X, y = G.simulate(1500, p, seed=7, fit_intercept=fi)
+    ref = G.fit("poisson", X, y, fit_intercept=fi)
     sk = lm.PoissonRegressor(alpha=0, solver="newton-cholesky", tol=1e-10, max_iter=1000,
                              fit_intercept=fi).fit(X, y)
     coef = np.concatenate([[sk.intercept_], sk.coef_]) if fi else sk.coef_
     print("rel", _rel(ref["theta"], coef), "iters", ref["iters"], "halvings", ref["halvings"])
     assert _rel(ref["theta"], coef) < 1e-9
     # the log-likelihood is the full one: it matches the definition at sklearn's coef
-    Z = R.design(X, fi)
-    assert abs(ref["loglik"] - R.loglik(Z, y, coef)) <= 1e-9 * abs(ref["loglik"])
-    assert ref["loglik"] >= R.loglik(Z, y, coef) - 1e-9 * abs(ref["loglik"])
+    Z = G.design(X, fi)
+    assert abs(ref["loglik"] - G.loglik("poisson", Z, y, coef)) <= 1e-9 * abs(ref["loglik"])
+    assert ref["loglik"] >= G.loglik("poisson", Z, y, coef) - 1e-9 * abs(ref["loglik"])
 
 
 def test_reference_start_and_halving():
     """The overshoot design of the GPU test: the reference has to halve."""
     th = np.zeros(10)
     th[0] = 1.2
-    X, y = R.simulate(8000, 10, seed=11, shift0=3.0, theta_true=th)
-    ref = R.fit(X, y)
+    X, y = G.simulate(8000, 10, seed=11, shift0=3.0, theta_true=th)
+    ref = G.fit("poisson", X, y)
     print("mean y", y.mean(), "halvings", ref["halvings"], "iters", ref["iters"])
     assert ref["halvings"] >= 1
     assert _rel(ref["theta"], th) < 0.1

@@ -1,5 +1,5 @@
 """Poisson regression with a per-row offset, CPU side: the numpy yardstick of
-tests/_poisson_offset_ref.py against scikit-learn, the C-ABI declarations of
+tests/_glm_ref.py (Poisson with an offset) against scikit-learn, the C-ABI declarations of
 the two new entry points and the Python surface."""
 
 import ctypes
@@ -10,7 +10,7 @@ import re
 import numpy as np
 import pytest
 
-import _poisson_offset_ref as RO
+import _glm_ref as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -26,32 +26,32 @@ def test_reference_vs_sklearn(p, fi):
     """A Poisson fit with offset log E has the MLE of the rate model: y / E
     with sample_weight E."""
     lm = pytest.importorskip("sklearn.linear_model")
-    X, y, o = RO.simulate(3001, p, fit_intercept=fi)
+    X, y, o = G.simulate_offset(3001, p, fit_intercept=fi)
     E = np.exp(o)
     assert E.min() >= 0.2 * (1 - 1e-12) and E.max() <= 5.0 * (1 + 1e-12)
-    ref = RO.fit(X, y, o, fit_intercept=fi)
+    ref = G.fit("poisson", X, y, o=o, fit_intercept=fi)
     sk = lm.PoissonRegressor(alpha=0, solver="newton-cholesky", tol=1e-10, max_iter=1000,
                              fit_intercept=fi).fit(X, y / E, sample_weight=E)
     coef = np.concatenate([[sk.intercept_], sk.coef_]) if fi else sk.coef_
     print("rel", _rel(ref["theta"], coef), "iters", ref["iters"], "halvings", ref["halvings"])
     assert _rel(ref["theta"], coef) < 1e-9
     # the offset matters on this data: the fit that ignores it is somewhere else
-    import _poisson_ref as R
-    assert _rel(R.fit(X, y, fit_intercept=fi)["theta"], ref["theta"]) > 1e-3
+    assert _rel(G.fit("poisson", X, y, fit_intercept=fi)["theta"], ref["theta"]) > 1e-3
 
 
 def test_reference_start_and_outputs():
-    X, y, o = RO.simulate(2000, 5, fit_intercept=True)
-    Z = RO.design(X, True)
-    t0 = RO.start(y, o, 6, True)
+    X, y, o = G.simulate_offset(2000, 5, fit_intercept=True)
+    Z = G.design(X, True)
+    t0 = G.start("poisson", y, 6, True, o=o)
     # the intercept-only rate MLE: its score sum(y - exp(t0 + o)) vanishes
     assert abs(np.sum(y - np.exp(t0[0] + o))) < 1e-9 * y.sum() and not t0[1:].any()
-    assert not RO.start(y, o, 5, False).any()
-    ref = RO.fit(X, y, o, fit_intercept=True)
+    assert not G.start("poisson", y, 5, False, o=o).any()
+    ref = G.fit("poisson", X, y, o=o, fit_intercept=True)
     mu = np.exp(Z @ ref["theta"] + o)
     assert np.abs(Z.T @ (y - mu)).max() < 1e-7 * y.sum()
     assert _rel(ref["sig_inv"], Z.T @ (Z * mu[:, None])) < 1e-14
-    assert abs(ref["loglik"] - RO.loglik(Z, y, o, ref["theta"])) < 1e-12 * abs(ref["loglik"])
+    ll = G.loglik("poisson", Z, y, ref["theta"], o=o)
+    assert abs(ref["loglik"] - ll) < 1e-12 * abs(ref["loglik"])
 
 
 def _decl(name):

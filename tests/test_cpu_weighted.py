@@ -1,5 +1,5 @@
 """Per-row prior weights without a GPU: the numpy yardstick of
-tests/_weighted_ref.py pinned against the unweighted references and against
+tests/_glm_ref.py with weights pinned against itself without them and against
 row replication, and the C-ABI / Python surface of the weighted entries.
 
 Both sides of every comparison are the same fp64 Newton run to convergence
@@ -14,8 +14,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import _poisson_offset_ref as RO
-import _weighted_ref as W
+import _glm_ref as G
 import oracle as O
 
 TOL = 1e-12
@@ -56,7 +55,7 @@ NONEMPTY = [k for k, s in enumerate(SIZES) if s > 0]
 @pytest.mark.parametrize("fi", [False, True])
 def test_unit_weights_logistic_is_the_oracle(fi):
     X, y, off = _logistic_data(6, SIZES)
-    got = W.fit_partitions("logistic", X, y, np.ones(len(y)), off, fit_intercept=fi)
+    got = G.fit_partitions("logistic", X, y, off, w=np.ones(len(y)), fit_intercept=fi)
     for k in NONEMPTY:
         o = O.logistic_fit(X[off[k]:off[k + 1]], y[off[k]:off[k + 1]], fit_intercept=fi,
                            tol=1e-12)
@@ -66,19 +65,19 @@ def test_unit_weights_logistic_is_the_oracle(fi):
 
 @pytest.mark.parametrize("fi,with_offset", [(False, False), (True, False), (True, True)])
 def test_unit_weights_poisson_is_the_offset_reference(fi, with_offset):
-    X, y, o = RO.simulate(int(sum(SIZES)), 5, fit_intercept=fi)
+    X, y, o = G.simulate_offset(int(sum(SIZES)), 5, fit_intercept=fi)
     off = _offsets(SIZES)
     if not with_offset:
         o0 = np.zeros_like(o)
         y = np.random.default_rng(5).poisson(np.exp(X[:, :2].sum(1) * 0.5 + fi)).astype(float)
     else:
         o0 = o
-    got = W.fit_partitions("poisson", X, y, np.ones(len(y)), off,
+    got = G.fit_partitions("poisson", X, y, off, w=np.ones(len(y)),
                            o=o0 if with_offset else None, fit_intercept=fi)
     want = {f: {} for f in ("theta", "sig_inv", "loglik")}
     for k in NONEMPTY:
         a, b = off[k], off[k + 1]
-        r = RO.fit(X[a:b], y[a:b], o0[a:b], fit_intercept=fi)
+        r = G.fit("poisson", X[a:b], y[a:b], o=o0[a:b], fit_intercept=fi)
         for f in want:
             want[f][k] = r[f]
     _same(got, want, NONEMPTY, f"poisson unit fi={fi} ofs={with_offset}")
@@ -91,21 +90,21 @@ def test_integer_weights_are_replication(family):
     fi = True
     off = _offsets(SIZES)
     n = int(off[-1])
-    w = W.weights(n, "int")
+    w = G.weights(n, "int")
     if family == "logistic":
         X, y, _ = _logistic_data(6, SIZES)
         o = None
     else:
-        X, y, o = RO.simulate(n, 5, fit_intercept=fi)
+        X, y, o = G.simulate_offset(n, 5, fit_intercept=fi)
         if family == "poisson":
             o = None
             y = np.random.default_rng(5).poisson(np.exp(X[:, :2].sum(1) * 0.5 + 1.0)).astype(float)
     fam = "logistic" if family == "logistic" else "poisson"
-    got = W.fit_partitions(fam, X, y, w, off, o=o, fit_intercept=fi)
+    got = G.fit_partitions(fam, X, y, off, w=w, o=o, fit_intercept=fi)
     arrays = (X, y) if o is None else (X, y, o)
-    rep = W.replicate(w, *arrays)
-    roff = W.replicate_offsets(w, off)
-    want = W.fit_partitions(fam, rep[0], rep[1], np.ones(len(rep[1])), roff,
+    rep = G.replicate(w, *arrays)
+    roff = G.replicate_offsets(w, off)
+    want = G.fit_partitions(fam, rep[0], rep[1], roff, w=np.ones(len(rep[1])),
                             o=None if o is None else rep[2], fit_intercept=fi)
     _same(got, want, NONEMPTY, f"{family} replication")
     # and the replicated side is the unweighted reference itself
@@ -116,7 +115,7 @@ def test_integer_weights_are_replication(family):
         assert _rel(want["theta"][k], r["coef"]) < TOL
     else:
         oo = np.zeros(b - a) if o is None else rep[2][a:b]
-        r = RO.fit(rep[0][a:b], rep[1][a:b], oo, fit_intercept=fi)
+        r = G.fit("poisson", rep[0][a:b], rep[1][a:b], o=oo, fit_intercept=fi)
         assert _rel(want["theta"][k], r["theta"]) < TOL
 
 
@@ -131,9 +130,9 @@ def test_grouped_binomial_is_the_expanded_fit():
     m = rng.integers(1, 6, n)
     prob = 1.0 / (1.0 + np.exp(-(0.3 + X[:, 0] - 0.5 * X[:, 1])))
     s = rng.binomial(m, prob)
-    got = W.fit_partitions("logistic", X, s / m, m.astype(float), off, fit_intercept=fi)
-    Xe, ye, offe = W.expand_binomial(X, s, m, off)
-    want = W.fit_partitions("logistic", Xe, ye, np.ones(len(ye)), offe, fit_intercept=fi)
+    got = G.fit_partitions("logistic", X, s / m, off, w=m.astype(float), fit_intercept=fi)
+    Xe, ye, offe = G.expand_binomial(X, s, m, off)
+    want = G.fit_partitions("logistic", Xe, ye, offe, w=np.ones(len(ye)), fit_intercept=fi)
     _same(got, want, NONEMPTY, "grouped binomial")
     k = NONEMPTY[0]
     r = O.logistic_fit(Xe[offe[k]:offe[k + 1]], ye[offe[k]:offe[k + 1]], fit_intercept=fi,

@@ -21,8 +21,8 @@ step.  It is copied into the case's workspace (repeated to length for the
 wide workspaces, which are larger), so every case meets the same image.
 
 Run A is compared with the yardstick of the test the case was taken from
-(``oracle.logistic_fit``, ``oracle.ols_fit``, ``_poisson_ref.fit``,
-``_poisson_offset_ref.fit``) at the suite's tolerances: theta, Sig_inv and
+(``oracle.logistic_fit``, ``oracle.ols_fit``, ``_glm_ref.fit``) at the suite's
+tolerances: theta, Sig_inv and
 Sig_inv theta within 1e-8 of the largest entry, the log-likelihood within
 1e-10 (the OLS rss within 1e-6, test_ols_vs_oracle: it is a difference of
 two sums).  That is the only numerical tolerance here; everything else is
@@ -258,8 +258,7 @@ def _eval_problem(kind, B):
     """Data, candidates and the oracle's [K, B] log-likelihoods; the loops of
     test_gpu_eval.py (categorical), test_gpu_poisson.py and
     test_gpu_poisson_offset.py (test_evaluation), oracle.logistic_loglik."""
-    import _poisson_offset_ref as RO
-    import _poisson_ref as R
+    import _glm_ref as G
 
     off = np.concatenate([[0], np.cumsum(EVAL_SIZES)]).astype(np.int64)
     n = int(off[-1])
@@ -288,17 +287,18 @@ def _eval_problem(kind, B):
         if kind.startswith("logistic"):
             X, y = O.simulate_counter(n, p, seed=9)
         else:
-            X, y = R.simulate(n, p, seed=9, fit_intercept=True)
+            X, y = G.simulate(n, p, seed=9, fit_intercept=True)
         X = np.ascontiguousarray(X)
         c, s = X.mean(0), X.std(0, ddof=1)
-        Z = R.design(X, True, c, s)
+        Z = G.design(X, True, c, s)
         if kind.startswith("logistic"):
             ref = np.array([O.logistic_loglik(Z[a:b], y[a:b], betas) for a, b in parts])
         elif kind == "poisson":
-            ref = np.array([[R.loglik(Z[a:b], y[a:b], bt) for bt in betas] for a, b in parts])
+            ref = np.array([[G.loglik("poisson", Z[a:b], y[a:b], bt) for bt in betas]
+                            for a, b in parts])
         else:
             o = P._eta_offset(n, p)
-            ref = np.array([[RO.loglik(Z[a:b], y[a:b], o[a:b], bt) for bt in betas]
+            ref = np.array([[G.loglik("poisson", Z[a:b], y[a:b], bt, o=o[a:b]) for bt in betas]
                             for a, b in parts])
             d["eta_offset"] = o
     d.update(X=X, y=np.ascontiguousarray(y, dtype=np.float64), center=c, scale=s,

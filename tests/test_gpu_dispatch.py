@@ -18,8 +18,7 @@ import functools
 import numpy as np
 import pytest
 
-import _poisson_offset_ref as RO
-import _poisson_ref as R
+import _glm_ref as G
 import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -87,14 +86,14 @@ def ols_case(NT):
 
 def poisson_case(NT):
     p, fi, sizes = _shape(NT)
-    X, y, off, ref = R.case(p, fi, sizes)
+    X, y, off, ref = G.case(p, fi, sizes)
     assert _usable(ref, ref["iters"], 200)
     return X, y, off, ref
 
 
 def poisson_offset_case(NT):
     p, fi, sizes = _shape(NT)
-    X, y, o, off, ref = RO.case(p, fi, sizes)
+    X, y, o, off, ref = G.case_offset(p, fi, sizes)
     assert _usable(ref, ref["iters"], 200)
     return X, y, o, off, ref
 

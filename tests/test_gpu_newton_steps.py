@@ -37,8 +37,8 @@ printed next to it.
 import numpy as np
 import pytest
 
+import _glm_ref as G
 import _newton_ref as N
-import _poisson_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -112,11 +112,11 @@ def _expected_passes(ys, m, nk):
 
 def _eval_at(fam, X, y, theta, fi, center, scale):
     """fp64 numpy Sig_inv, Sig_inv theta and log-likelihood at a given theta."""
-    Z = R.design(X, fi, center, scale)
+    Z = G.design(X, fi, center, scale)
     eta = Z @ theta
     _, w = N.weights(fam, eta)
     S = Z.T @ (Z * w[:, None])
-    ll = R.loglik(Z, y, theta) if fam == "poisson" else N.loglik(fam, eta, y)
+    ll = G.loglik("poisson", Z, y, theta) if fam == "poisson" else N.loglik(fam, eta, y)
     return S, S @ theta, ll
 
 
@@ -291,7 +291,7 @@ def test_many_partitions_poisson(torch_cuda, M):
     assert fit.status.cpu().numpy().tolist() == [OK] * K
     for k in N.MANY_SAMPLE:
         a, b = off[k], off[k + 1]
-        ref = R.fit(X[a:b], y[a:b], fit_intercept=True)
+        ref = G.fit("poisson", X[a:b], y[a:b], fit_intercept=True)
         e = (_rel(fit.theta[k].cpu(), ref["theta"]), _rel(fit.sig_inv[k].cpu(), ref["sig_inv"]),
              _rel(fit.sig_inv_theta[k].cpu(), ref["sig_inv_theta"]),
              abs(float(fit.loglik[k]) - ref["loglik"]) / abs(ref["loglik"]))

@@ -1,6 +1,6 @@
 """Poisson family on the GPU: the HIP fit (dlsa_poisson_fit_batched_ex through
 models.poisson_model_batched) against the numpy fp64 Newton yardstick of
-tests/_poisson_ref.py.
+tests/_glm_ref.py.
 
 Tolerances are the project's (tests/test_gpu_parity.py): theta, Sig_inv,
 Sig_invMcoef and the WLSE within 1e-8 of the reference relative to the largest
@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 import pytest
 
-import _poisson_ref as R
+import _glm_ref as G
 import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -65,7 +65,7 @@ CASES = [(p, fi, "mixed") for p, fi in SHAPES] + [(16, False, "fp64"), (100, Tru
 def test_shapes(M, p, fi, hessian):
     """NT = 1..12, both exact-pass kernels (per-wave up to P = 128, cooperative
     fp64 above), block tails under 8 rows, chunks of 1000 rows."""
-    X, y, off, ref = R.case(p, fi, _sizes(p))
+    X, y, off, ref = G.case(p, fi, _sizes(p))
     fit = M.poisson_model_batched(X, y, off, fit_intercept=fi, hessian=hessian,
                                   rows_per_chunk=1000)
     print("stats", {k: fit.stats[k] for k in ("iterations", "passes_fp32", "passes_fp64",
@@ -82,20 +82,20 @@ def test_shapes(M, p, fi, hessian):
 def test_halving_needed_by_reference():
     """The shapes meant to exercise the halving path do so in the reference."""
     for p in (129, 192):
-        _, _, _, ref = R.case(p, False, _sizes(p))
+        _, _, _, ref = G.case(p, False, _sizes(p))
         assert ref["halvings"].sum() >= 1
 
 
 def test_standardised_intercept(M):
     p = 37
     off = np.concatenate([[0], np.cumsum(SIZES)]).astype(np.int64)
-    X, _ = R.simulate(int(off[-1]), p, seed=5)
+    X, _ = G.simulate(int(off[-1]), p, seed=5)
     X = X * np.linspace(0.5, 3.0, p) + np.linspace(-1.0, 2.0, p)  # columns worth standardising
     center, scale = X.mean(0), X.std(0, ddof=1)
     b = np.zeros(p)
     b[:14] = 0.5
     y = np.random.default_rng(5).poisson(np.exp(1.0 + ((X - center) / scale) @ (b * 0.3))).astype(float)
-    ref = R.fit_partitions(X, y, off, fit_intercept=True, center=center, scale=scale)
+    ref = G.fit_partitions("poisson", X, y, off, fit_intercept=True, center=center, scale=scale)
     fit = M.poisson_model_batched(X, y, off, fit_intercept=True, center=center, scale=scale,
                                   rows_per_chunk=1000)
     assert fit.status.cpu().numpy().tolist() == [0, 0, 0, 0]
@@ -109,11 +109,11 @@ def test_overshoot(M, fi):
     th = np.zeros(10)
     th[0] = 1.2
     if fi:
-        X, y = R.simulate(8000, 10, seed=11, fit_intercept=True, intercept=4.0)
+        X, y = G.simulate(8000, 10, seed=11, fit_intercept=True, intercept=4.0)
     else:
-        X, y = R.simulate(8000, 10, seed=11, shift0=3.0, theta_true=th)
+        X, y = G.simulate(8000, 10, seed=11, shift0=3.0, theta_true=th)
     off = np.array([0, 8000], dtype=np.int64)
-    ref = R.fit_partitions(X, y, off, fit_intercept=fi)
+    ref = G.fit_partitions("poisson", X, y, off, fit_intercept=fi)
     print("mean y", y.mean(), "ref halvings", ref["halvings"])
     if not fi:
         assert ref["halvings"][0] >= 3
@@ -129,9 +129,9 @@ def test_overflowing_step(M, hessian):
     overshoot to halve (the reference halves nine times), not a NONFINITE end."""
     th = np.zeros(5)
     th[0] = 2.3
-    X, y = R.simulate(4000, 5, seed=13, shift0=3.0, theta_true=th)
+    X, y = G.simulate(4000, 5, seed=13, shift0=3.0, theta_true=th)
     off = np.array([0, 4000], dtype=np.int64)
-    ref = R.fit_partitions(X, y, off)
+    ref = G.fit_partitions("poisson", X, y, off)
     assert ref["halvings"][0] >= 5
     fit = M.poisson_model_batched(X, y, off, hessian=hessian)
     assert fit.status.cpu().numpy().tolist() == [0]
@@ -140,7 +140,7 @@ def test_overflowing_step(M, hessian):
 
 def test_warm_start_level(M):
     sizes = (6000, 5000, 0)
-    X, y, off, ref = R.case(12, True, sizes[:2])
+    X, y, off, ref = G.case(12, True, sizes[:2])
     off3 = np.concatenate([off, off[-1:]])
     n = int(off3[-1])
     fit = M.poisson_model_batched(X, y, off3, fit_intercept=True)
@@ -158,7 +158,7 @@ def test_bad_partitions(M, order):
     from dlsa_amd.dlsa import dlsa_mapred
 
     p, m = 8, 2000
-    Xs, ys = R.simulate(4 * m, p, seed=3)
+    Xs, ys = G.simulate(4 * m, p, seed=3)
     blocks = []
     for j in range(4):
         Xb, yb = Xs[j * m:(j + 1) * m], ys[j * m:(j + 1) * m].copy()
@@ -173,7 +173,7 @@ def test_bad_partitions(M, order):
     want = {0: 0, 1: NONFINITE, 2: SINGULAR, 3: 0}
     good = [i for i, j in enumerate(order) if want[j] == 0]
     bad = [i for i, j in enumerate(order) if want[j] != 0]
-    ref = {i: R.fit(X[off[i]:off[i + 1]], y[off[i]:off[i + 1]]) for i in good}
+    ref = {i: G.fit("poisson", X[off[i]:off[i + 1]], y[off[i]:off[i + 1]]) for i in good}
     fit = M.poisson_model_batched(X, y, off)
     assert fit.status.cpu().numpy().tolist() == [want[j] for j in order]
     for i in good:
@@ -204,7 +204,7 @@ def test_limit(M):
 
 
 def test_determinism(M):
-    X, y, off, _ = R.case(100, True, SIZES)
+    X, y, off, _ = G.case(100, True, SIZES)
     a = M.poisson_model_batched(X, y, off, fit_intercept=True, rows_per_chunk=1000)
     b = M.poisson_model_batched(X, y, off, fit_intercept=True, rows_per_chunk=1000)
     for f in ("theta", "sig_inv", "sig_inv_theta", "loglik", "iters", "status"):
@@ -216,10 +216,10 @@ def test_job_level(M, fi):
     from dlsa_amd.distributed import dlsa_fit_sharded
 
     n, p, K = 100000, 10, 4
-    X, y = R.simulate(n, p, seed=2019, fit_intercept=fi)
+    X, y = G.simulate(n, p, seed=2019, fit_intercept=fi)
     order, off = O.systematic_partition(np.arange(n) % K)
     X, y = X[order], y[order]
-    ref = R.fit_partitions(X, y, off, fit_intercept=fi)
+    ref = G.fit_partitions("poisson", X, y, off, fit_intercept=fi)
     out = dlsa_fit_sharded(X, y, off, fit_intercept=fi, family="poisson")
     assert out["fit"].status.cpu().numpy().tolist() == [0] * K
     wlse, _, S = O.dlsa_mapred(ref["theta"], ref["sig_inv"])
@@ -236,7 +236,7 @@ def test_plain_c_abi(M):
 
     from dlsa_amd import _hip
 
-    X, y, off, ref = R.case(10, False, SIZES)
+    X, y, off, ref = G.case(10, False, SIZES)
     dev = torch.device("cuda")
     Xd, yd = torch.from_numpy(X).to(dev), torch.from_numpy(y).to(dev)
     K, P = 4, 10
@@ -262,12 +262,12 @@ def test_plain_c_abi(M):
 def test_evaluation(M, B):
     p = 37
     off = np.concatenate([[0], np.cumsum(SIZES)]).astype(np.int64)
-    X, y = R.simulate(int(off[-1]), p, seed=9, fit_intercept=True)
+    X, y = G.simulate(int(off[-1]), p, seed=9, fit_intercept=True)
     center, scale = X.mean(0), X.std(0, ddof=1)
     rng = np.random.default_rng(B)
     betas = 0.2 * rng.standard_normal((B, p + 1))
-    Z = R.design(X, True, center, scale)
-    want = np.array([[R.loglik(Z[a:b], y[a:b], bt) for bt in betas]
+    Z = G.design(X, True, center, scale)
+    want = np.array([[G.loglik("poisson", Z[a:b], y[a:b], bt) for bt in betas]
                      for a, b in zip(off[:-1], off[1:])])
     got, tot = M.poisson_loglik_batched(X, y, off, betas, fit_intercept=True, center=center,
                                         scale=scale, return_sum=True)

@@ -1,7 +1,7 @@
 """Poisson regression with a per-row offset on the GPU: the HIP fit
 (dlsa_poisson_fit_batched_offset through models.poisson_model_batched_offset)
 and evaluation pass against the numpy fp64 yardstick of
-tests/_poisson_offset_ref.py.
+tests/_glm_ref.py.
 
 Tolerances are those of tests/test_gpu_poisson.py: theta, Sig_inv and
 Sig_inv theta within 1e-8 of the reference relative to the largest entry, the
@@ -11,8 +11,7 @@ log-likelihood within 1e-10 relative, statuses and supports exact.
 import numpy as np
 import pytest
 
-import _poisson_offset_ref as RO
-import _poisson_ref as R
+import _glm_ref as G
 import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -70,7 +69,7 @@ def test_shapes(M, p, fi, hessian):
     """W = 4 and W = 8 of the cooperative pass, its three precisions, both
     exact-pass kernels, the strip and no-strip per-wave geometries; chunks of
     1000 rows, so every chunk ends inside a block."""
-    X, y, o, off, ref = RO.case(p, fi, _sizes(p))
+    X, y, o, off, ref = G.case_offset(p, fi, _sizes(p))
     fit = M.poisson_model_batched_offset(X, y, off, eta_offset=o, fit_intercept=fi,
                                          hessian=hessian, rows_per_chunk=1000)
     print("stats", {k: fit.stats[k] for k in ("iterations", "passes_fp32", "passes_fp64",
@@ -88,7 +87,7 @@ def test_standardised_intercept(M):
     p = 37
     off = np.concatenate([[0], np.cumsum(SIZES)]).astype(np.int64)
     n = int(off[-1])
-    X, _ = R.simulate(n, p, seed=5)
+    X, _ = G.simulate(n, p, seed=5)
     X = X * np.linspace(0.5, 3.0, p) + np.linspace(-1.0, 2.0, p)  # columns worth standardising
     center, scale = X.mean(0), X.std(0, ddof=1)
     b = np.zeros(p)
@@ -96,7 +95,8 @@ def test_standardised_intercept(M):
     o = np.random.default_rng(1000 + p).uniform(np.log(0.2), np.log(5.0), n)
     y = np.random.default_rng(5).poisson(
         np.exp(1.0 + ((X - center) / scale) @ (b * 0.3) + o)).astype(float)
-    ref = RO.fit_partitions(X, y, o, off, fit_intercept=True, center=center, scale=scale)
+    ref = G.fit_partitions("poisson", X, y, off, o=o, fit_intercept=True, center=center,
+                           scale=scale)
     fit = M.poisson_model_batched_offset(X, y, off, eta_offset=o, fit_intercept=True,
                                          center=center, scale=scale, rows_per_chunk=1000)
     assert fit.status.cpu().numpy().tolist() == [0, 0, 0, 0]
@@ -107,10 +107,11 @@ def test_standardised_intercept(M):
 
 def _one_partition(p, fi):
     n = 3001 if p <= 128 else 12005
-    X, y, o = RO.simulate(n, p, fit_intercept=fi)
-    Z = RO.design(X, fi)
-    th0 = RO.start(y, o, Z.shape[1], fi)
-    return X, y, o, Z, th0, RO.newton_step(Z, y, o, th0), np.array([0, n], dtype=np.int64)
+    X, y, o = G.simulate_offset(n, p, fit_intercept=fi)
+    Z = G.design(X, fi)
+    th0 = G.start("poisson", y, Z.shape[1], fi, o=o)
+    step = G.newton_step("poisson", Z, y, th0, o=o)
+    return X, y, o, Z, th0, step, np.array([0, n], dtype=np.int64)
 
 
 def _bf16(a32):
@@ -152,8 +153,8 @@ def test_approximate_hessian_sees_offset(M, p, fi):
     assert d_gpu <= 10 * d_bf16
     # what the polish pass publishes: Sig_inv and loglik at the returned theta
     assert fit.status.cpu().numpy().tolist() == [MAXITER]
-    assert _rel(fit.sig_inv[0].cpu().numpy(), RO.hessian(Z, o, th1)) < REL
-    want = RO.loglik(Z, y, o, th1)
+    assert _rel(fit.sig_inv[0].cpu().numpy(), G.hessian("poisson", Z, th1, o=o)) < REL
+    want = G.loglik("poisson", Z, y, th1, o=o)
     assert abs(float(fit.loglik[0]) - want) < REL_LL * abs(want)
 
 
@@ -173,7 +174,7 @@ def test_equivalences(M):
     import torch
 
     p, fi = 20, True
-    X, y, off, _ = R.case(p, fi, SIZES)
+    X, y, off, _ = G.case(p, fi, SIZES)
     n = int(off[-1])
     base = M.poisson_model_batched(X, y, off, fit_intercept=fi, rows_per_chunk=1000)
     assert base.status.cpu().numpy().tolist() == [0, 0, 0, 0]
@@ -206,7 +207,7 @@ def test_equivalences(M):
     close(const, shifted, "constant offset")
 
     # exposure = E is eta_offset = log E, the log taken on the device
-    Xo, yo, oo, offo, _ = RO.case(p, fi, SIZES)
+    Xo, yo, oo, offo, _ = G.case_offset(p, fi, SIZES)
     E = torch.from_numpy(np.exp(oo)).to(base.theta.device)
     a = M.poisson_model_batched_offset(Xo, yo, offo, exposure=E, fit_intercept=fi,
                                        rows_per_chunk=1000)
@@ -228,7 +229,7 @@ def test_bad_offset(M, bad, hessian):
     from dlsa_amd.dlsa import dlsa_mapred
 
     sizes, p = (1500, 2000, 2003), 8
-    X, y, o, off, ref = RO.case(p, True, sizes)
+    X, y, o, off, ref = G.case_offset(p, True, sizes)
     ob = o.copy()
     ob[off[1]] = bad
     fit = M.poisson_model_batched_offset(X, y, off, eta_offset=ob, fit_intercept=True,
@@ -248,7 +249,7 @@ def test_bad_offset(M, bad, hessian):
 # ---- 6. warm-start level ---------------------------------------------------------
 
 def test_warm_start_level(M):
-    X, y, o, off, ref = RO.case(12, True, (6000, 5000))
+    X, y, o, off, ref = G.case_offset(12, True, (6000, 5000))
     off3 = np.concatenate([off, off[-1:]])
     n = int(off3[-1])
     fit = M.poisson_model_batched_offset(X, y, off3, eta_offset=o, fit_intercept=True)
@@ -269,15 +270,15 @@ def test_evaluation(M, p):
     import torch
 
     sizes = (1500, 777, 2003)
-    X, y, o, off, ref = RO.case(p, True, sizes)
+    X, y, o, off, ref = G.case_offset(p, True, sizes)
     if p + 1 <= 192:
         fit = M.poisson_model_batched_offset(X, y, off, eta_offset=o, fit_intercept=True)
         th = fit.theta[0].cpu().numpy()
     else:
         fit, th = None, ref["theta"][0]
     betas = np.stack([th, 0.9 * th, np.zeros(p + 1)])
-    Z = RO.design(X, True)
-    want = np.array([[RO.loglik(Z[a:b], y[a:b], o[a:b], bt) for bt in betas]
+    Z = G.design(X, True)
+    want = np.array([[G.loglik("poisson", Z[a:b], y[a:b], bt, o=o[a:b]) for bt in betas]
                      for a, b in zip(off[:-1], off[1:])])
     got, tot = M.poisson_loglik_batched_offset(X, y, off, betas, eta_offset=o,
                                                fit_intercept=True, return_sum=True)
@@ -303,10 +304,10 @@ def test_job_level(M):
     from dlsa_amd.distributed import dlsa_fit_sharded
 
     n, p, K, fi = 100000, 10, 4, True
-    X, y, o = RO.simulate(n, p, fit_intercept=fi, seed=2019)
+    X, y, o = G.simulate_offset(n, p, fit_intercept=fi, seed=2019)
     order, off = O.systematic_partition(np.arange(n) % K)
     X, y, o = X[order], y[order], o[order]
-    ref = RO.fit_partitions(X, y, o, off, fit_intercept=fi)
+    ref = G.fit_partitions("poisson", X, y, off, o=o, fit_intercept=fi)
     out = dlsa_fit_sharded(X, y, off, fit_intercept=fi, family="poisson", exposure=np.exp(o))
     assert out["fit"].status.cpu().numpy().tolist() == [0] * K
     wlse, _, S = O.dlsa_mapred(ref["theta"], ref["sig_inv"])

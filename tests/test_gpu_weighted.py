@@ -3,7 +3,7 @@
 dlsa_amd.models) and the weighted evaluation pass.
 
 Yardsticks: the library's own unweighted fit of the row-replicated data (both
-sides on the GPU) and the numpy fp64 Newton of tests/_weighted_ref.py.
+sides on the GPU) and the numpy fp64 Newton of tests/_glm_ref.py.
 Tolerances are the project's contracts: theta and Sig_inv theta within 1e-8
 relative to the largest entry, Sig_inv per entry |d_ij| / sqrt(H_ii H_jj) <
 1e-10, the log-likelihood within 1e-9 relative; statuses equal.
@@ -28,8 +28,7 @@ import functools
 import numpy as np
 import pytest
 
-import _poisson_offset_ref as RO
-import _weighted_ref as W
+import _glm_ref as G
 import oracle as O
 from _poison import FUSED_SIZES, FUSED_SIZES_BIG, STATUS_EMPTY, STATUS_NONFINITE, \
     STATUS_SINGULAR, bits_equal
@@ -89,7 +88,7 @@ def _data(family, p, fi):
         b[:max(1, int(0.4 * p))] = 1.0
         s = rng.binomial(m, 1.0 / (1.0 + np.exp(-(X @ b + (0.3 if fi else 0.0)))))
         return X, s.astype(np.float64), m.astype(np.float64), off
-    X, y, o = RO.simulate(n, p, fit_intercept=fi)
+    X, y, o = G.simulate_offset(n, p, fit_intercept=fi)
     if family == "poisson":
         b = np.zeros(p)
         b[:max(1, int(0.4 * p))] = 0.5
@@ -151,11 +150,11 @@ def test_replication(M, family, p, fi, hessian, kind):
     left out.  In mixed mode iters agree within one: an omega missing from
     the bf16 image would still converge through the exact gradient, but later."""
     X, y, o, off = _data(family, p, fi)
-    w = W.weights(len(y), kind)
+    w = G.weights(len(y), kind)
     got = _host(_fit(M, family, X, y, o, off, fi, hessian, w=w))
     arrays = (X, y) if o is None else (X, y, o)
-    rep = W.replicate(w, *arrays)
-    roff = W.replicate_offsets(w, off)
+    rep = G.replicate(w, *arrays)
+    roff = G.replicate_offsets(w, off)
     want = _host(_fit(M, family, rep[0], rep[1], None if o is None else rep[2], roff, fi, hessian))
     assert want["status"].tolist() == [0, STATUS_EMPTY, 0, 0, 0]
     _compare(got, want, f"rep {family} p={p} fi={fi} {hessian} {kind}", iters_pm1=hessian == "mixed")
@@ -166,7 +165,7 @@ def test_grouped_binomial(M, p, fi):
     """y = s / m with omega = m against the expanded 0/1 rows."""
     X, s, m, off = _data("binomial", p, fi)
     got = _host(_fit(M, "logistic", X, s / m, None, off, fi, "mixed", w=m))
-    Xe, ye, offe = W.expand_binomial(X, s, m, off)
+    Xe, ye, offe = G.expand_binomial(X, s, m, off)
     want = _host(_fit(M, "logistic", Xe, ye, None, offe, fi, "mixed"))
     _compare(got, want, f"binomial p={p} fi={fi}", iters_pm1=True)
 
@@ -185,7 +184,7 @@ REAL = [
 @pytest.mark.parametrize("family,p,fi,hessian,std", REAL)
 def test_real_weights(M, family, p, fi, hessian, std):
     X, y, o, off = _data(family, p, fi)
-    w = W.weights(len(y), "real")
+    w = G.weights(len(y), "real")
     kw = {}
     if std:  # columns worth standardising
         X = X * np.linspace(0.5, 3.0, p) + np.linspace(-1.0, 2.0, p)
@@ -195,7 +194,7 @@ def test_real_weights(M, family, p, fi, hessian, std):
                 0.5 + 0.3 * ((X - kw["center"]) / kw["scale"])[:, :4].sum(1)
                 + (0.0 if o is None else o))).astype(float)
     fam = "logistic" if family == "logistic" else "poisson"
-    ref = W.fit_partitions(fam, X, y, w, off, o=o, fit_intercept=fi, **kw)
+    ref = G.fit_partitions(fam, X, y, off, w=w, o=o, fit_intercept=fi, **kw)
     fit = _fit(M, family, X, y, o, off, fi, hessian, w=w, **kw)
     got = _host(fit)
     assert got["status"].tolist() == [0, STATUS_EMPTY, 0, 0, 0]
@@ -292,10 +291,10 @@ def test_bad_weight(M, family, bad, where, hessian):
         X, y = O.simulate_counter(n, p, seed=5)
         o = None
     else:
-        X, y, o = RO.simulate(n, p, fit_intercept=fi)
+        X, y, o = G.simulate_offset(n, p, fit_intercept=fi)
     import torch
 
-    w = W.weights(n, "real").copy()
+    w = G.weights(n, "real").copy()
     wb = w.copy()
     wb[{"first": off[1], "middle": (off[1] + off[2]) // 2, "last": off[2] - 1}[where]] = bad
     with pytest.raises(ValueError, match="sample_weight"):  # the Python layer refuses it
@@ -326,8 +325,8 @@ def test_zero_weight_partition_is_singular(M, family):
     if family == "logistic":
         X, y = O.simulate_counter(n, p, seed=5)
     else:
-        X, y, _ = RO.simulate(n, p, fit_intercept=fi)
-    w = W.weights(n, "real").copy()
+        X, y, _ = G.simulate_offset(n, p, fit_intercept=fi)
+    w = G.weights(n, "real").copy()
     clean = _host(_fit(M, family, X, y, None, off, fi, "mixed", w=w))
     w[off[1]:off[2]] = 0.0
     got = _host(_fit(M, family, X, y, None, off, fi, "mixed", w=w))
@@ -347,17 +346,17 @@ def test_evaluation(M, family, p):
     zeros) per partition and summed, against numpy to 1e-12 relative."""
     fi = True
     X, y, o, off = _data(family, p, fi)
-    w = W.weights(len(y), "real")
+    w = G.weights(len(y), "real")
     fit = _fit(M, family, X, y, o, off, fi, "mixed", w=w)
     th = fit.theta[0].cpu().numpy()
     betas = np.stack([th, 0.9 * th, np.zeros(p + 1)])
-    Z = W.design(X, fi)
+    Z = G.design(X, fi)
     parts = [k for k in range(len(off) - 1) if off[k + 1] > off[k]]
 
     def ll(a, b, bt):
         if family == "logistic":
-            return W.logistic_loglik(Z[a:b], y[a:b], w[a:b], bt)
-        return W.poisson_loglik(Z[a:b], y[a:b], w[a:b], bt, None if o is None else o[a:b])
+            return G.loglik("logistic", Z[a:b], y[a:b], bt, w[a:b])
+        return G.loglik("poisson", Z[a:b], y[a:b], bt, w[a:b], None if o is None else o[a:b])
 
     want = np.array([[ll(off[k], off[k + 1], bt) for bt in betas] for k in parts])
     kw = dict(fit_intercept=fi, return_sum=True, sample_weight=w)
@@ -388,7 +387,7 @@ def test_workspace_hygiene(M, family):
 
     p, fi = 100, True
     X, y, o, off = _data(family, p, fi)
-    w = W.weights(len(y), "real")
+    w = G.weights(len(y), "real")
     other = "poisson" if family == "logistic" else "logistic"
     Xs, ys, _, offs = _data(other, 129, False)
     lib = _hip.load()
@@ -450,7 +449,7 @@ def test_sharded(M, family):
 
     p, fi = 13, True
     X, y, o, off = _data(family, p, fi)
-    w = W.weights(len(y), "real")
+    w = G.weights(len(y), "real")
     out = dlsa_fit_sharded(X, y, off, fit_intercept=fi, family=family, sample_weight=w,
                            rows_per_chunk=RPC, tol=TOL)
     fit = _fit(M, family, X, y, o, off, fi, "mixed", w=w)
@@ -464,6 +463,6 @@ def test_sharded(M, family):
     if family == "logistic":
         betas = np.stack([out["wlse"], out["beta_byBIC"]])
         tot = loglik_sharded(X, y, off, betas, fit_intercept=fi, sample_weight=w)
-        Z = W.design(X, fi)
-        ref = np.array([W.logistic_loglik(Z, y, w, b) for b in betas])
+        Z = G.design(X, fi)
+        ref = np.array([G.loglik("logistic", Z, y, b, w) for b in betas])
         assert (np.abs(tot / ref - 1) < 1e-12).all()
