@@ -39,6 +39,7 @@
 #include <math.h>
 
 #include "dlsa_internal.hpp"
+#include "glm_row.hpp"
 
 // Profiling-only ablation bits (tools/build_variants.sh cat*; product build 0):
 // 1 no numeric x dummy histogram adds, 2 no pair adds, 4 no gradient adds,
@@ -244,12 +245,10 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(const CatArgs a) {
 #pragma unroll
     for (int f = 0; f < FM; ++f) e0 += de[f];
     const double e = e0 + e1;
-    const double ea = exp(-fabs(e));
-    const double inv = 1.0 / (1.0 + ea);
-    const double mu = e >= 0.0 ? inv : ea * inv;
-    const double w = ea * inv * inv;  // mu (1 - mu), cancellation free
-    const double res = yv - mu;
-    llacc += yv * e - (fmax(e, 0.0) + log1p(ea));
+    const LogisticLink k = logistic_link<RCP_DIV>(e);
+    const double w = k.w;
+    const double res = yv - k.mu;
+    llacc += yv * e - (fmax(e, 0.0) + log1p(k.ea));
 
 #pragma unroll
     for (int i = Q0; i < QN && !(DLSA_CAT_ABLATE & 8); ++i) {

@@ -14,6 +14,7 @@
 // reads.  Each chunk writes one partial per candidate and its count of codes
 // >= levels[f] (looked up as code 0); no atomics.
 #include "dlsa_internal.hpp"
+#include "glm_row.hpp"
 
 namespace dlsa {
 
@@ -199,7 +200,7 @@ __global__ __launch_bounds__(256) void loglik_cat_kernel(const EvalCatArgs a) {
     for (int b = 0; b < BP; ++b) {
       if (b < B) {
         const double e = eta[b];
-        if (valid) llacc[b] += yv * e - (fmax(e, 0.0) + log1p(exp(-fabs(e))));
+        if (valid) llacc[b] += row_loglik<FAMILY_LOGISTIC>(e, yv, 1.0, 0.0);
       }
     }
   }

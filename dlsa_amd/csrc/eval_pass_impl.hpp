@@ -4,6 +4,7 @@
 #pragma once
 
 #include "dlsa_internal.hpp"
+#include "glm_row.hpp"
 
 namespace dlsa {
 
@@ -12,23 +13,16 @@ namespace {
 constexpr int EW = 4;    // waves
 constexpr int ERB = 32;  // rows per block
 constexpr int EMAXB = 16;
-
-__device__ __forceinline__ double ev_red8(double v) {
-  v += dpp_f64<0xB1>(v);
-  v += dpp_f64<0x4E>(v);
-  v += dpp_f64<0x141>(v);
-  return v;
-}
 __host__ __device__ __forceinline__ int ev_npieces(int p) {
   return (ERB * p * 8 + 16 + 1023) / 1024;
 }
 
 }  // namespace
 
-// (each row extra, EX_*: ERB doubles behind y, the offsets first)
+// (the X pieces, a pad, then the row streams: y and the row extras, glm_row.hpp)
 inline int eval_slot_bytes_impl(int p, int n_extras) {
   const int d = (ev_npieces(p) + EW - 1) / EW;
-  return 16 + d * EW * 1024 + ((p + 8) / 8) * 8 * 8 + ERB * 8 + n_extras * ERB * 8;
+  return 16 + d * EW * 1024 + ((p + 8) / 8) * 8 * 8 + row_streams_bytes(n_extras);
 }
 // dynamic LDS of a launch: the ring, the candidates, center / 1/scale, the reduction
 inline size_t eval_lds_bytes(const EvalArgs& a) {
@@ -40,15 +34,16 @@ inline size_t eval_lds_bytes(const EvalArgs& a) {
 // FAM: FAMILY_LOGISTIC, or FAMILY_POISSON (y eta - exp(eta) - lgamma(y + 1), the
 // full log-likelihood; the constant once per row, not per candidate).
 // EX (row extras, EX_* mask), each streamed like y, one more load per wave
-// and block: EX_OFS (FAMILY_POISSON only) a.eta_offset[row] is added to every
+// and block (the layout and the readers of RowStreams; the loads here address
+// with clamped global pointers): EX_OFS (FAMILY_POISSON only) a.eta_offset[row] is added to every
 // candidate's eta; EX_WGT every term of the row is multiplied by
 // a.row_weight[row] (the weighted kernels take EvalArgsWgt).
 template <int FAM, int EX = EX_NONE>
 __global__ __launch_bounds__(256) void loglik_eval_kernel(const typename eval_args_of<EX>::type a) {
-  constexpr bool OFS = (EX & EX_OFS) != 0, WGT = (EX & EX_WGT) != 0;
+  using RS = RowStreams<EX>;
+  constexpr bool OFS = RS::OFS, WGT = RS::WGT;
   static_assert(!OFS || FAM == FAMILY_POISSON, "the offset is the Poisson family's");
-  constexpr int NLD = 1 + ex_count(EX);  // loads per block beside X: y and the row extras
-  constexpr int WOFF = ERB * (1 + (OFS ? 1 : 0));  // doubles from y to the weights in a slot
+  constexpr int NLD = RS::NLD;  // loads per block beside X: y and the row extras
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int chunk = blockIdx.x;
   const int part = a.chunk_part[chunk];
@@ -100,14 +95,14 @@ __global__ __launch_bounds__(256) void loglik_eval_kernel(const typename eval_ar
     if constexpr (OFS) {
       uintptr_t os = (uintptr_t)(a.eta_offset + row0 + (int64_t)bb * ERB) + (uintptr_t)lane * 4;
       os = os < a.o_last4 ? os : a.o_last4;
-      __builtin_amdgcn_global_load_lds((gbl_void_t*)os, (lds_void_t*)(sbase + slot_x + ERB * 8),
+      __builtin_amdgcn_global_load_lds((gbl_void_t*)os, (lds_void_t*)(sbase + slot_x + RS::OFS_OFF),
                                        4, 0, 0);
     }
     if constexpr (WGT) {
       uintptr_t wsrc = (uintptr_t)(a.row_weight + row0 + (int64_t)bb * ERB) + (uintptr_t)lane * 4;
       wsrc = wsrc < a.w_last4 ? wsrc : a.w_last4;
       __builtin_amdgcn_global_load_lds((gbl_void_t*)wsrc,
-                                       (lds_void_t*)(sbase + slot_x + WOFF * 8), 4, 0, 0);
+                                       (lds_void_t*)(sbase + slot_x + RS::WGT_OFF), 4, 0, 0);
     }
   };
 
@@ -149,10 +144,9 @@ __global__ __launch_bounds__(256) void loglik_eval_kernel(const typename eval_ar
     }
     const double yv = ys[rB];
     [[maybe_unused]] double ov = 0.0;
-    if constexpr (OFS) ov = ys[ERB + rB];
-    // (a padded row's weight, possibly the next partition's NaN, stays behind `valid`)
+    if constexpr (OFS) ov = RS::offset(ys, rB);
     [[maybe_unused]] double om = 1.0;
-    if constexpr (WGT) om = valid ? ys[WOFF + rB] : 0.0;
+    if constexpr (WGT) om = valid ? ys[RS::WGT_OFF / 8 + rB] : 0.0;
     double lg = 0.0;  // lgamma(y + 1): 0 at y = 0 and y = 1
     if constexpr (FAM == FAMILY_POISSON)
       if (valid && sl == 0 && yv != 0.0 && yv != 1.0) lg = lgamma1p(yv);
@@ -161,16 +155,7 @@ __global__ __launch_bounds__(256) void loglik_eval_kernel(const typename eval_ar
       if (b < B) {
         double e = ev_red8(eta[b]);
         if constexpr (OFS) e += ov;
-        if constexpr (FAM == FAMILY_POISSON && WGT) {
-          if (valid && sl == 0) llacc[b] += om * (yv * e - exp(e) - lg);
-        } else if constexpr (FAM == FAMILY_POISSON) {
-          if (valid && sl == 0) llacc[b] += yv * e - exp(e) - lg;
-        } else if constexpr (WGT) {
-          if (valid && sl == 0)
-            llacc[b] += om * (yv * e - (fmax(e, 0.0) + log1p(exp(-fabs(e)))));
-        } else {
-          if (valid && sl == 0) llacc[b] += yv * e - (fmax(e, 0.0) + log1p(exp(-fabs(e))));
-        }
+        if (valid && sl == 0) llacc[b] += row_loglik<FAM>(e, yv, om, lg);
       }
     }
   }

@@ -1,0 +1,64 @@
+// The device-side statement of the GLM families' row expressions, beside
+// FamilyRules (dlsa_internal.hpp) and tests/_glm_ref.py, and the layout of the
+// per-row streams (y and the row extras) in the tail of a ring slot.  Values
+// in, values out; the `if (valid && lane sums)` stays at the call site.
+#pragma once
+
+#include "dlsa_internal.hpp"
+#include "wave_math.hpp"
+
+namespace dlsa {
+
+// Behind the X pieces of a slot: y, then each row extra in bit order (EX_OFS
+// the offset, EX_WGT the prior weight), each kRowStreamRows doubles, one 4-byte
+// LDS-DMA load per lane and block.
+constexpr int kRowStreamRows = 32;
+// bytes of the slot tail of a pass with n_extras row extras (the slot sizes)
+constexpr int row_streams_bytes(int n_extras) { return (1 + n_extras) * kRowStreamRows * 8; }
+
+template <int EX>
+struct RowStreams {
+  static constexpr bool OFS = (EX & EX_OFS) != 0, WGT = (EX & EX_WGT) != 0;
+  static constexpr int NLD = 1 + ex_count(EX);  // loads per block beside X: y and the extras
+  static constexpr int OFS_OFF = row_streams_bytes(0);  // byte offsets in the tail; y at 0
+  static constexpr int WGT_OFF = row_streams_bytes(OFS ? 1 : 0);
+  // ys: the tail (the block's y); row: the row of the block
+  static __device__ __forceinline__ double offset(const double* ys, int row) {
+    return ys[OFS_OFF / 8 + row];
+  }
+  // The weight is read as `valid ? ys[WGT_OFF / 8 + row] : 0.0`, one line in
+  // each kernel (as a function it changes the spill count of two cooperative
+  // kernels): a padded row's is the next partition's, possibly NaN, and
+  // 0 * NaN would reach w, r and the sums.  Its offset and y need no select:
+  // they stay behind the row phase's selects on `valid`.  An unweighted kernel
+  // multiplies by the constant om = 1, which folds away.
+};
+
+// The reciprocal of 1 + exp(-|eta|), kept where each was measured: the library
+// division, or wv_rcp.
+enum : int { RCP_DIV = 0, RCP_NEWTON = 1 };
+
+// Logistic link at eta = e: ea = exp(-|e|), mu, w = mu (1 - mu) without
+// cancellation.  (The int8 producer, irls_oz_impl.hpp, takes sqrt(w) through
+// the half angle and states these lines itself; simulate_y_kernel draws y from
+// 1 / (1 + exp(-eta)), which the oracle restates bit for bit.)
+struct LogisticLink { double ea, mu, w; };
+template <int RCP>
+__device__ __forceinline__ LogisticLink logistic_link(double e) {
+  const double ea = exp(-fabs(e));
+  const double inv = RCP == RCP_NEWTON ? wv_rcp(1.0 + ea) : 1.0 / (1.0 + ea);
+  return {ea, e >= 0.0 ? inv : ea * inv, ea * inv * inv};
+}
+
+// One row's term of the evaluation passes at eta = e; lg = lgamma(y + 1) is
+// computed once per row by the caller (0 for the logistic family); om the
+// prior weight (the constant 1 without one).
+template <int FAM>
+__device__ __forceinline__ double row_loglik(double e, double yv, double om, double lg) {
+  if constexpr (FAM == FAMILY_POISSON)
+    return om * (yv * e - exp(e) - lg);
+  else
+    return om * (yv * e - (fmax(e, 0.0) + log1p(exp(-fabs(e)))));
+}
+
+}  // namespace dlsa

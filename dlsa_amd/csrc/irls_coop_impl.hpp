@@ -32,6 +32,7 @@
 #pragma once
 
 #include "dlsa_internal.hpp"
+#include "glm_row.hpp"
 
 namespace dlsa {
 
@@ -55,36 +56,6 @@ constexpr int RB = kCoopRows;   // rows per block
 // semi-definite by construction, as in the wide fused pass), instead of the
 // two images x and w x -- half the image stores and LDS: 9.87 -> 9.37 ms per
 // config-2 launch (profiles/r02ac_zimage_ab.txt)
-
-// Lane l and lane l ^ 16 (permlane16_swap), l and l ^ 32 (permlane32_swap):
-// both operands are v, so the swapped pair (x, y) holds the two halves and
-// x + y is the same sum, bitwise, in both lanes of the pair.
-__device__ __forceinline__ double xor16_sum(double v) {
-  const unsigned lo = __double2loint(v), hi = __double2hiint(v);
-  const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-__device__ __forceinline__ double xor32_sum(double v) {
-  const unsigned lo = __double2loint(v), hi = __double2hiint(v);
-  const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-
-// Sum over the lanes l, l ^ RPW, l ^ 2 RPW, ... (the LPR feature groups of one
-// row in the row phase) without LDS: row_ror 8 (and 4) inside a 16-lane DPP
-// row, then the cross-row swaps.  Every lane of the row ends with the
-// bitwise-identical total (each step adds a commutative pair).
-template <int RPW>
-__device__ __forceinline__ double red_row(double v) {
-  static_assert(RPW == 8 || RPW == 4, "4 or 8 rows per wave");
-  v += dpp_f64<0x128>(v);                         // row_ror 8: l ^ 8
-  if constexpr (RPW == 4) v += dpp_f64<0x124>(v);  // row_ror 4: l + 4, l + 12
-  v = xor16_sum(v);
-  v = xor32_sum(v);
-  return v;
-}
 
 constexpr int tile_I(int t) {
   int I = 0;
@@ -134,11 +105,12 @@ constexpr int coop_waves(int NT) { return NT > 8 ? 8 : 4; }
 // A slot holds exactly the block's pieces: a wave's surplus issues (the piece
 // count is rounded up to the wave count so that every wave waits on the same
 // vmcnt) re-load the last piece onto itself.
-// Each row extra (the Poisson offset, the prior weights: EX_*) adds its RB
-// doubles behind y.  (constexpr for coop_ring_fits below, so npieces_for(p)
-// is spelled out)
+// Behind them, PMAX doubles of pad and the row streams: y and the row extras
+// (glm_row.hpp).  (constexpr for coop_ring_fits below, so npieces_for(p) is
+// spelled out)
+static_assert(RB == kRowStreamRows, "a block's rows are one row stream of the slot");
 constexpr int coop_slot_bytes_impl(int NT, int p, int n_extras = 0) {
-  return 16 + ((RB * p * 8 + 16 + 1023) / 1024) * 1024 + 16 * NT * 8 + RB * 8 + n_extras * RB * 8;
+  return 16 + ((RB * p * 8 + 16 + 1023) / 1024) * 1024 + 16 * NT * 8 + row_streams_bytes(n_extras);
 }
 
 // LDS beyond the ring: w, r of the block [2][RB] fp64, center / 1/scale
@@ -233,8 +205,8 @@ __device__ __forceinline__ void store_tiles(Acc (&acc)[(CG<NT, W>::TPW)], double
 // value of the bf16 image) into a.zcolmax (2: the bf16 passes of partitions
 // near convergence); the Ozaki exact pass takes its digit scales from the
 // last records (irls_oz_impl.hpp)
-// EX (row extras, EX_* mask): each streams like y, one more DMA piece of
-// RB * 8 bytes per block behind y, the offset first.
+// EX (row extras, EX_* mask): each streams like y, one more load per wave and
+// block behind y (RowStreams, glm_row.hpp).
 //   EX_OFS (FAMILY_POISSON only): eta = x . theta + a.eta_offset[row]
 //   EX_WGT: prior weights omega = a.row_weight[row]: w, r and the row's
 //   log-likelihood terms are multiplied by omega once, after mu (so the bf16 /
@@ -246,15 +218,14 @@ void irls_coop_kernel(const typename pass_args_of<EX>::type a) {
   using Acc = typename std::conditional<PREC == PREC_F64, d4, f4>::type;
   constexpr int RPW = G::RPW, LPR = G::LPR;
   constexpr int M = G::M;
-  constexpr bool OFS = (EX & EX_OFS) != 0, WGT = (EX & EX_WGT) != 0;
-  static_assert(!OFS || FAM == FAMILY_POISSON, "the offset is the Poisson family's");
-  static_assert(!WGT || CM == 0, "no digit-scale records of a weighted pass");
-  constexpr int NLD = 1 + ex_count(EX);       // loads per block beside X: y and the row extras
+  using RS = RowStreams<EX>;
+  static_assert(!RS::OFS || FAM == FAMILY_POISSON, "the offset is the Poisson family's");
+  static_assert(!RS::WGT || CM == 0, "no digit-scale records of a weighted pass");
+  constexpr int NLD = RS::NLD;                // loads per block beside X: y and the row extras
   constexpr int MAXW = 4 * (G::MAX_D + NLD);  // nslot <= 6
   // a wave has at most nslot - 1 <= 5 blocks of d + NLD <= MAX_D + NLD loads
   // outstanding: within the 6-bit vmcnt (5 (9 + 3) = 60 at NT = 8 with both extras)
   static_assert(5 * (G::MAX_D + NLD) <= 63, "outstanding loads exceed the vmcnt counter");
-  constexpr int WOFF = RB * (1 + (OFS ? 1 : 0));  // doubles from y to the weights in a slot
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int chunk = blockIdx.x;
@@ -349,12 +320,12 @@ void irls_coop_kernel(const typename pass_args_of<EX>::type a) {
   const __amdgpu_buffer_rsrc_t yr_rsrc = uniform_rsrc(ycb, a.y_last4 + 4 - ycb);
   const int vx = lane * 16, vy = lane * 4;
   [[maybe_unused]] __amdgpu_buffer_rsrc_t or_rsrc;
-  if constexpr (OFS) {
+  if constexpr (RS::OFS) {
     const uintptr_t ocb = (uintptr_t)(a.eta_offset + row0);
     or_rsrc = uniform_rsrc(ocb, a.o_last4 + 4 - ocb);
   }
   [[maybe_unused]] __amdgpu_buffer_rsrc_t wr_rsrc;
-  if constexpr (WGT) {
+  if constexpr (RS::WGT) {
     const uintptr_t wcb = (uintptr_t)(a.row_weight + row0);
     wr_rsrc = uniform_rsrc(wcb, a.w_last4 + 4 - wcb);
   }
@@ -372,12 +343,12 @@ void irls_coop_kernel(const typename pass_args_of<EX>::type a) {
     }
     __builtin_amdgcn_raw_ptr_buffer_load_lds(yr_rsrc, (lds_void_t*)(sbase + slot_x), 4, vy,
                                              bb * RB * 8, 0, 0);
-    if constexpr (OFS)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(or_rsrc, (lds_void_t*)(sbase + slot_x + RB * 8), 4,
-                                               vy, bb * RB * 8, 0, 0);
-    if constexpr (WGT)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(wr_rsrc, (lds_void_t*)(sbase + slot_x + WOFF * 8),
-                                               4, vy, bb * RB * 8, 0, 0);
+    if constexpr (RS::OFS)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(
+          or_rsrc, (lds_void_t*)(sbase + slot_x + RS::OFS_OFF), 4, vy, bb * RB * 8, 0, 0);
+    if constexpr (RS::WGT)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(
+          wr_rsrc, (lds_void_t*)(sbase + slot_x + RS::WGT_OFF), 4, vy, bb * RB * 8, 0, 0);
   };
 
   // every wave issues d + NLD loads per block, in block order: with at most
@@ -430,35 +401,30 @@ void irls_coop_kernel(const typename pass_args_of<EX>::type a) {
         else
           e0 = fma(v, beta[m], e0);
       }
-      double e = red_row<RPW>(e0 + e1);  // bitwise-identical in all lanes of the row
+      // bitwise-identical in all lanes of the row
+      double e = wv_row_sum<RPW, true>(e0 + e1);
       // the offset once, after the reduction (every lane of the row adds the
       // same value); a padded row's may be the next partition's, even NaN: the
       // selects on `valid` below keep it out of w, r and the log-likelihood
-      if constexpr (OFS) e += ys[RB + rB];
+      if constexpr (RS::OFS) e += RS::offset(ys, rB);
       const double yv = ys[rB];
-      // the prior weight, selected on `valid`: a padded row's is the next
-      // partition's (possibly NaN) and reaches nothing
-      [[maybe_unused]] double om = 1.0;
-      if constexpr (WGT) om = valid ? ys[WOFF + rB] : 0.0;
+      // the prior weight (RowStreams, glm_row.hpp); 1 folds out of the products
+      double om = 1.0;
+      if constexpr (RS::WGT) om = valid ? ys[RS::WGT_OFF / 8 + rB] : 0.0;
       double w, r;
       if constexpr (FAM == FAMILY_LOGISTIC && DLSA_ABLATE == 2) {
         w = 0.25;
         r = yv - 0.5 - 0.25 * e;
         if (valid && sl == 0) llacc += e;
       } else if constexpr (FAM == FAMILY_LOGISTIC) {
-        const double ea = exp(-fabs(e));
-        const double inv = 1.0 / (1.0 + ea);
-        const double mu = e >= 0.0 ? inv : ea * inv;
-        w = ea * inv * inv;  // mu (1 - mu), cancellation free
-        r = yv - mu;
+        const LogisticLink k = logistic_link<RCP_DIV>(e);
+        w = k.w;
+        r = yv - k.mu;
         if (valid && sl == 0) {
           // exact fp64 in the fp64 pass (its value is returned); fp32 log in
           // the approximate passes, where it only drives step halving
-          const double sp = (PREC == PREC_F64) ? log1p(ea) : (double)__logf(1.0f + (float)ea);
-          if constexpr (WGT)
-            llacc += om * (yv * e - (fmax(e, 0.0) + sp));
-          else
-            llacc += yv * e - (fmax(e, 0.0) + sp);
+          const double sp = (PREC == PREC_F64) ? log1p(k.ea) : (double)__logf(1.0f + (float)k.ea);
+          llacc += om * (yv * e - (fmax(e, 0.0) + sp));
         }
       } else if constexpr (FAM == FAMILY_POISSON) {
         // log link: mu = w = exp(eta).  A padded row's eta is never
@@ -470,27 +436,17 @@ void irls_coop_kernel(const typename pass_args_of<EX>::type a) {
         w = mu;
         r = yv - mu;
         if (valid && sl == 0) {
-          if constexpr (WGT)
-            llacc += om * (yv * e - mu);
-          else
-            llacc += yv * e - mu;
-          if constexpr (PREC == PREC_F64) {
-            if constexpr (WGT) {
-              if (yv != 0.0 && yv != 1.0) llcacc -= om * lgamma1p(yv);
-            } else {
-              if (yv != 0.0 && yv != 1.0) llcacc -= lgamma1p(yv);  // 0 at y = 0, 1
-            }
-          }
+          llacc += om * (yv * e - mu);
+          if constexpr (PREC == PREC_F64)
+            if (yv != 0.0 && yv != 1.0) llcacc -= om * lgamma1p(yv);  // 0 at y = 0, 1
         }
       } else {  // gaussian (OLS): mu = eta, w = 1, ll = -rss/2
         w = 1.0;
         r = yv - e;
         if (valid && sl == 0) llacc -= 0.5 * r * r;
       }
-      if constexpr (WGT) {  // once, after mu; ahead of the padded rows' zeroing
-        w *= om;
-        r *= om;
-      }
+      w *= om;  // once, after mu; ahead of the padded rows' zeroing
+      r *= om;
       if (!valid) {
         w = 0.0;
         r = 0.0;

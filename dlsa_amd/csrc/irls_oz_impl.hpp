@@ -62,7 +62,8 @@
 #include <array>
 #include <utility>
 
-#include "irls_wave_impl.hpp"
+#include "dlsa_internal.hpp"
+#include "wave_math.hpp"
 
 namespace dlsa {
 
@@ -486,6 +487,8 @@ __device__ __forceinline__ void oz_producer(const PassArgs& a, char* smem, int w
     {
       const bool valid = rbase + myrow < leftq;
       const double yv = valid ? yq[rbase + myrow] : 0.0;
+      // logistic_link (glm_row.hpp) through the half angle: eqv = sqrt(ea)
+      // gives sqrt(w) = eqv * inv without a square root
       const double eqv = exp(-0.5 * fabs(eh));
       const double ea = eqv * eqv;
       const double inv = wv_rcp(1.0 + ea);

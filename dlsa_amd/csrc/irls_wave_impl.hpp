@@ -37,96 +37,24 @@
 #include <utility>
 
 #include "dlsa_internal.hpp"
+#include "glm_row.hpp"
 
 namespace dlsa {
 
 typedef double wd4 __attribute__((ext_vector_type(4)));
-
-namespace {
-
-__device__ __forceinline__ double wv_xor16(double v) {
-  const unsigned lo = __double2loint(v), hi = __double2hiint(v);
-  const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-__device__ __forceinline__ double wv_xor32(double v) {
-  const unsigned lo = __double2loint(v), hi = __double2hiint(v);
-  const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-// The value of lane l ^ 32.  v_permlane32_swap exchanges lanes 32-63 of vdst
-// with lanes 0-31 of src: with both = v, vdst holds the partner's value in
-// the upper half and src in the lower half.
-__device__ __forceinline__ double wv_swap32(double v, bool upper) {
-  const unsigned lo = __double2loint(v), hi = __double2hiint(v);
-  const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  return upper ? __hiloint2double(b[0], a[0]) : __hiloint2double(b[1], a[1]);
-}
-
-// Sum over the LPR lanes of one row (lanes l, l + R, l + 2R, ...); every lane
-// of the row ends with the bitwise-identical total (each step adds a
-// commutative pair).
-template <int R>
-__device__ __forceinline__ double wv_row_sum(double v) {
-  static_assert(R == 16 || R == 8 || R == 4, "16, 8 or 4 rows per block");
-  if constexpr (R == 4) v += __shfl_xor(v, 4);   // l ^ 4 (no DPP form)
-  if constexpr (R <= 8) v += dpp_f64<0x128>(v);  // row_ror 8: l ^ 8
-  v = wv_xor16(v);
-  v = wv_xor32(v);
-  return v;
-}
-
-// 1 / d for d in [1, 3]: hardware estimate + two Newton steps (~1 ulp; the
-// library division's scaling / fix-up steps are for operands this never sees)
-__device__ __forceinline__ double wv_rcp(double d) {
-  double r = __builtin_amdgcn_rcp(d);
-  r = fma(r, fma(-d, r, 1.0), r);
-  r = fma(r, fma(-d, r, 1.0), r);
-  return r;
-}
-
-// log(t) for t in [1, 2] (t = 1 + exp(-|eta|): the softplus of the
-// log-likelihood).  t -> t / 2 above sqrt 2, then log t = k ln 2 + 2 atanh(s),
-// s = (t - 1) / (t + 1) in [-0.172, 0.172], by the odd series to s^19
-// (truncation < 1e-17 relative).  A few ulps, against ~70 instructions of the
-// double-double library log1p; log1p's extra accuracy for tiny arguments is
-// not needed here: the terms are summed, so the absolute error (~1e-16 per
-// row) is what counts.
-__device__ __forceinline__ double wv_log12(double t) {
-  const bool hi = t > 1.4142135623730951;
-  const double u = hi ? 0.5 * t : t;
-  const double s = (u - 1.0) * wv_rcp(u + 1.0);
-  const double s2 = s * s;
-  double q = 1.0 / 19.0;
-  q = fma(q, s2, 1.0 / 17.0);
-  q = fma(q, s2, 1.0 / 15.0);
-  q = fma(q, s2, 1.0 / 13.0);
-  q = fma(q, s2, 1.0 / 11.0);
-  q = fma(q, s2, 1.0 / 9.0);
-  q = fma(q, s2, 1.0 / 7.0);
-  q = fma(q, s2, 1.0 / 5.0);
-  q = fma(q, s2, 1.0 / 3.0);
-  const double l = fma(2.0 * s * s2, q, 2.0 * s);
-  return hi ? l + 0.6931471805599453094 : l;
-}
-
-}  // namespace
 
 // Ring slots per workgroup: one block in flight while the current one is
 // computed.  Three slots (two blocks in flight) for the OLS pass (8-row, 4 KiB
 // blocks at P = 64) measured slower (config-4 pass 16.7-17.1 vs 14.9-15.2 ms,
 // profiles/r04h_ols_ab.txt).
 constexpr int kWaveSlots = 2;
-// Ring slot: [16 B pad][npieces KiB of X rows][256 B: y of up to 32 rows]
-// (then 256 B per row extra, EX_*: the rows' offsets, the rows' prior weights)
+// Ring slot: [16 B pad][npieces KiB of X rows][the row streams: y, the row
+// extras (glm_row.hpp)]
 __host__ __device__ __forceinline__ int wave_npieces(int RB, int p) {
   return (RB * p * 8 + 16 + 1023) / 1024;
 }
 __host__ __device__ __forceinline__ int wave_slot_bytes_impl(int RB, int p, int n_extras = 0) {
-  return 16 + wave_npieces(RB, p) * 1024 + 256 + n_extras * 256;
+  return 16 + wave_npieces(RB, p) * 1024 + row_streams_bytes(n_extras);
 }
 // LDS of one workgroup: 2 ring slots + w of a block [RB] + theta [PMAX] +
 // center / 1/scale [2][PMAX]
@@ -268,15 +196,14 @@ struct WaveCtx {
 
 // The block loop + epilogue of wave WID (a separate code path per wave: no
 // branch merges of the accumulator arrays).
-// EX (row extras, EX_* mask), each streamed like y into 256 B behind it, the
-// offset first: EX_OFS (FAMILY_POISSON only) eta = x . theta +
+// EX (row extras, EX_* mask), each streamed like y behind it (RowStreams,
+// glm_row.hpp): EX_OFS (FAMILY_POISSON only) eta = x . theta +
 // a.eta_offset[row]; EX_WGT prior weights omega = a.row_weight[row], which
 // multiply w, r and the row's log-likelihood terms once, after mu.
 template <int NT, int NS, int W, int WID, bool STD, int FAM, int EX = EX_NONE>
 __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, char* smem) {
   using TL = WaveTiles<NT, NS, W, WID>;
-  constexpr bool OFS = (EX & EX_OFS) != 0, WGT = (EX & EX_WGT) != 0;
-  constexpr int WOFF = 32 * (1 + (OFS ? 1 : 0));  // doubles from y to the weights in a slot
+  using RS = RowStreams<EX>;
   // strip tiles (the last tile row as NS 4x4x4_4b sub-blocks)
   constexpr auto strip = [](int I) { return NS > 0 && I == NT - 1; };
   constexpr bool HAS_STRIP = NS > 0 && ((TL::RM >> (NT - 1)) & 1u);
@@ -321,8 +248,8 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
     for (int r = 0; r < NSA; ++r) sacc[i][r] = 0.0;
   }
 
-  // DMA: wave WID issues pieces j = WID, WID + W, ...; the last wave also y
-  // (and the offset: the wait below is for all of a wave's loads)
+  // DMA: wave WID issues pieces j = WID, WID + W, ...; the last wave also the
+  // row streams (the wait below is for all of a wave's loads)
   auto issue = [&](int blk) {
     char* sbase = smem + (blk % kWaveSlots) * cx.slot_bytes;
     const uintptr_t start = (uintptr_t)(a.X + (cx.row0 + (int64_t)blk * RB) * p);
@@ -333,15 +260,16 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
     if (WID == W - 1)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.yr, (lds_void_t*)(sbase + cx.slot_y), 4,
                                                lane * 4, blk * RB * 8, 0, 0);
-    if constexpr (OFS)
+    if constexpr (RS::OFS)
       if (WID == W - 1)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.orr, (lds_void_t*)(sbase + cx.slot_y + 256),
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.orr,
+                                                 (lds_void_t*)(sbase + cx.slot_y + RS::OFS_OFF),
                                                  4, lane * 4, blk * RB * 8, 0, 0);
-    if constexpr (WGT)
+    if constexpr (RS::WGT)
       if (WID == W - 1)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(cx.wrr,
-                                                 (lds_void_t*)(sbase + cx.slot_y + WOFF * 8), 4,
-                                                 lane * 4, blk * RB * 8, 0, 0);
+                                                 (lds_void_t*)(sbase + cx.slot_y + RS::WGT_OFF),
+                                                 4, lane * 4, blk * RB * 8, 0, 0);
   };
 
   const int fl = lane & 15, q = lane >> 4;
@@ -404,51 +332,35 @@ __device__ __forceinline__ void wave_body(const PassArgs& a, const WaveCtx& cx, 
       double e = ETA0 ? 0.0 : wv_row_sum<RW>(e0 + e1);
       // the offset once, after the reduction; a padded row's (possibly the
       // next partition's, even NaN) stays behind the selects on `valid`
-      if constexpr (OFS) e += ys[32 + row];
+      if constexpr (RS::OFS) e += RS::offset(ys, row);
       const double yv = ys[row];
-      // the prior weight, selected on `valid`: a padded row's is the next
-      // partition's (possibly NaN) and reaches nothing
-      [[maybe_unused]] double om = 1.0;
-      if constexpr (WGT) om = valid ? ys[WOFF + row] : 0.0;
+      // the prior weight (RowStreams, glm_row.hpp); 1 folds out of the products
+      double om = 1.0;
+      if constexpr (RS::WGT) om = valid ? ys[RS::WGT_OFF / 8 + row] : 0.0;
       double w, r;
       if constexpr (FAM == FAMILY_LOGISTIC) {
-        const double ea = exp(-fabs(e));
-        const double inv = wv_rcp(1.0 + ea);
-        const double mu = e >= 0.0 ? inv : ea * inv;
-        w = ea * inv * inv;  // mu (1 - mu), cancellation free
-        r = yv - mu;
-        if (valid && sl == 0) {
-          if constexpr (WGT)
-            llacc += om * (yv * e - (fmax(e, 0.0) + wv_log12(1.0 + ea)));
-          else
-            llacc += yv * e - (fmax(e, 0.0) + wv_log12(1.0 + ea));
-        }
+        const LogisticLink k = logistic_link<RCP_NEWTON>(e);
+        w = k.w;
+        r = yv - k.mu;
+        if (valid && sl == 0)
+          llacc += om * (yv * e - (fmax(e, 0.0) + wv_log12(1.0 + k.ea)));
       } else if constexpr (FAM == FAMILY_POISSON) {
-        // log link: mu = w = exp(eta); a padded row's eta is never
-        // exponentiated.  llacc is the constant-free sum y eta - mu (what the
-        // step halving compares, as in the approximate passes); the constant
-        // -lgamma(y + 1) has its own sum, added where loglik is published
+        // log link, as in the cooperative pass: a padded row's eta is never
+        // exponentiated; the constant -lgamma(y + 1) has its own sum
         const double mu = exp(valid ? e : 0.0);
         w = mu;
         r = yv - mu;
         if (valid && sl == 0) {
-          if constexpr (WGT) {
-            llacc += om * (yv * e - mu);
-            if (yv != 0.0 && yv != 1.0) llcacc -= om * lgamma1p(yv);
-          } else {
-            llacc += yv * e - mu;
-            if (yv != 0.0 && yv != 1.0) llcacc -= lgamma1p(yv);  // 0 at y = 0, 1
-          }
+          llacc += om * (yv * e - mu);
+          if (yv != 0.0 && yv != 1.0) llcacc -= om * lgamma1p(yv);  // 0 at y = 0, 1
         }
       } else {  // gaussian (OLS): mu = eta, w = 1, ll = -rss / 2
         w = 1.0;
         r = yv - e;
         if (valid && sl == 0) llacc -= 0.5 * r * r;
       }
-      if constexpr (WGT) {  // once, after mu; ahead of the padded rows' zeroing
-        w *= om;
-        r *= om;
-      }
+      w *= om;  // once, after mu; ahead of the padded rows' zeroing
+      r *= om;
       if (!valid) {
         w = 0.0;
         r = 0.0;
@@ -591,8 +503,8 @@ constexpr int wave_min_waves(int NT, int W, int FAM) {
 template <int NT, int NS, int W, bool STD, int FAM, int EX = EX_NONE>
 __global__ __launch_bounds__(64 * W, wave_min_waves(NT, W, FAM)) void irls_wave_kernel(
     const typename pass_args_of<EX>::type a) {
-  constexpr bool OFS = (EX & EX_OFS) != 0, WGT = (EX & EX_WGT) != 0;
-  static_assert(!OFS || FAM == FAMILY_POISSON, "the offset is the Poisson family's");
+  static_assert(!RowStreams<EX>::OFS || FAM == FAMILY_POISSON,
+                "the offset is the Poisson family's");
   constexpr int RB = wave_rb(NT, W, FAM);
   constexpr int PMAX = 16 * NT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -634,11 +546,11 @@ __global__ __launch_bounds__(64 * W, wave_min_waves(NT, W, FAM)) void irls_wave_
   cx.xr = uniform_rsrc(cx.xcb, a.x_last16 + 16 - cx.xcb);
   const uintptr_t ycb = (uintptr_t)(a.y + cx.row0);
   cx.yr = uniform_rsrc(ycb, a.y_last4 + 4 - ycb);
-  if constexpr (OFS) {
+  if constexpr (RowStreams<EX>::OFS) {
     const uintptr_t ocb = (uintptr_t)(a.eta_offset + cx.row0);
     cx.orr = uniform_rsrc(ocb, a.o_last4 + 4 - ocb);
   }
-  if constexpr (WGT) {
+  if constexpr (RowStreams<EX>::WGT) {
     const uintptr_t wcb = (uintptr_t)(a.row_weight + cx.row0);
     cx.wrr = uniform_rsrc(wcb, a.w_last4 + 4 - wcb);
   }

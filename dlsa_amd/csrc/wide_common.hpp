@@ -35,23 +35,13 @@
 #pragma once
 
 #include "dlsa_internal.hpp"
+#include "wave_math.hpp"  // wave_sum64, bcast_first
 
 namespace dlsa {
 
 typedef double d4w __attribute__((ext_vector_type(4)));
 
 constexpr int GT = kWideTile;  // gram output tile edge (128)
-
-__device__ __forceinline__ double wave_sum64(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-__device__ __forceinline__ double bcast_first(double v) {
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
 
 // lower-triangle tile t -> (I, J), I >= J, row-major over I
 __device__ __forceinline__ void tile_ij(int t, int& I, int& J) {

@@ -4,7 +4,7 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "irls_wave_impl.hpp"  // wv_* wave helpers
+#include "glm_row.hpp"
 #include "wide_common.hpp"
 
 namespace dlsa {
@@ -77,12 +77,10 @@ __global__ __launch_bounds__(256) void wide_row_kernel(const WideArgs a) {
       e = bcast_first(wave_sum64(e));  // one value for the whole wave
       double w, r;
       if constexpr (FAM == FAMILY_LOGISTIC) {
-        const double ea = exp(-fabs(e));
-        const double inv = 1.0 / (1.0 + ea);
-        const double mu = e >= 0.0 ? inv : ea * inv;
-        w = ea * inv * inv;  // mu (1 - mu), cancellation free
-        r = yv[u] - mu;
-        if (valid && lane == 0) llacc += yv[u] * e - (fmax(e, 0.0) + log1p(ea));
+        const LogisticLink k = logistic_link<RCP_DIV>(e);
+        w = k.w;
+        r = yv[u] - k.mu;
+        if (valid && lane == 0) llacc += yv[u] * e - (fmax(e, 0.0) + log1p(k.ea));
       } else {  // gaussian (OLS): w = 1, ll = -rss/2
         w = 1.0;
         r = yv[u] - e;

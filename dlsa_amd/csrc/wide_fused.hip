@@ -3,7 +3,7 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "irls_wave_impl.hpp"  // wv_* wave helpers
+#include "glm_row.hpp"
 #include "wide_common.hpp"
 
 namespace dlsa {
@@ -303,11 +303,9 @@ __global__ __launch_bounds__(64 * FW, 1) void wide_fused_bf16_kernel(const WideA
     }
     const double eu = reduce_scatter8(e8, lane) + eoff;  // row rl of the wave
     const bool vrow = 32 * b + 8 * wid + rl < nrows;
-    const double ea = exp(-fabs(eu));
-    const double inv = wv_rcp(1.0 + ea);
-    const double mu = eu >= 0.0 ? inv : ea * inv;
-    const double w = ea * inv * inv;  // mu (1 - mu), cancellation free
-    const double r = vrow ? yv - mu : 0.0;
+    const LogisticLink k = logistic_link<RCP_NEWTON>(eu);
+    const double ea = k.ea, w = k.w;
+    const double r = vrow ? yv - k.mu : 0.0;
     if (sg == 0 && (lane & 7) == 0 && vrow) {
       llacc += yv * eu - fmax(eu, 0.0);
       lprod *= 1.0 + ea;

@@ -263,7 +263,7 @@ def _eval_problem(kind, B):
     off = np.concatenate([[0], np.cumsum(EVAL_SIZES)]).astype(np.int64)
     n = int(off[-1])
     parts = list(zip(off[:-1], off[1:]))
-    d = dict(off=off, codes=None, eta_offset=None, levels=(), fi=True)
+    d = dict(off=off, codes=None, eta_offset=None, row_weight=None, levels=(), fi=True)
     if kind == "cat":
         rs = np.random.RandomState(3070 + B)
         q, levels = 3, (7, 4)
@@ -291,7 +291,18 @@ def _eval_problem(kind, B):
         X = np.ascontiguousarray(X)
         c, s = X.mean(0), X.std(0, ddof=1)
         Z = G.design(X, True, c, s)
-        if kind.startswith("logistic"):
+        if kind.endswith("weighted_nan_behind"):
+            # a NaN weight in the first row of partition 1: the last block of
+            # partition 0 (5000 rows: 8 of a 32-row block) reads it as a padded row
+            fam = kind.split("_")[0]
+            w = G.weights(n, "real").copy()
+            o = P._eta_offset(n, p) if fam == "poisson" else None
+            ref = np.array([[G.loglik(fam, Z[a:b], y[a:b], bt, w[a:b],
+                                      None if o is None else o[a:b]) for bt in betas]
+                            for a, b in parts])
+            w[off[1]] = np.nan
+            d.update(eta_offset=o, row_weight=w)
+        elif kind.startswith("logistic"):
             ref = np.array([O.logistic_loglik(Z[a:b], y[a:b], betas) for a, b in parts])
         elif kind == "poisson":
             ref = np.array([[G.loglik("poisson", Z[a:b], y[a:b], bt) for bt in betas]
@@ -300,6 +311,9 @@ def _eval_problem(kind, B):
             o = P._eta_offset(n, p)
             ref = np.array([[G.loglik("poisson", Z[a:b], y[a:b], bt, o=o[a:b]) for bt in betas]
                             for a, b in parts])
+            if kind == "poisson_offset_nan_behind":  # the same row, a NaN offset
+                o = o.copy()
+                o[off[1]] = np.nan
             d["eta_offset"] = o
     d.update(X=X, y=np.ascontiguousarray(y, dtype=np.float64), center=c, scale=s,
              betas=np.ascontiguousarray(betas), ref=ref, p=X.shape[1])
@@ -307,11 +321,16 @@ def _eval_problem(kind, B):
 
 
 @pytest.mark.parametrize("B", [3, 17])
-@pytest.mark.parametrize("kind", ["logistic", "logistic_sum", "poisson", "poisson_offset", "cat"])
+@pytest.mark.parametrize("kind", ["logistic", "logistic_sum", "poisson", "poisson_offset", "cat",
+                                  "poisson_offset_nan_behind", "logistic_weighted_nan_behind",
+                                  "poisson_weighted_nan_behind"])
 def test_eval_buffers(env, kind, B):
     """[K, B] and [B] outputs poisoned, candidates in groups of at most 16 (the
     ABI's limit, as the Python layer calls it), an empty partition whose row is
-    exactly 0, a one-row partition at the buffers' end."""
+    exactly 0, a one-row partition at the buffers' end.  The ``*_nan_behind``
+    kinds put a NaN offset / prior weight directly behind partition 0's last
+    row: partition 1 is NaN, every other partition is the yardstick's."""
+    nan_part = 1 if kind.endswith("nan_behind") else -1
     d = _eval_problem(kind, B)
     K, off = len(EVAL_SIZES), d["off"]
     offp = off.ctypes.data_as(ctypes.c_void_p)
@@ -320,7 +339,7 @@ def test_eval_buffers(env, kind, B):
     A = P.Arena(env.device)
     A.add("X", d["X"].nbytes, 16, 8).add("y", d["y"].nbytes)
     A.add("center", d["center"].nbytes).add("scale", d["scale"].nbytes)
-    for name in ("codes", "eta_offset"):
+    for name in ("codes", "eta_offset", "row_weight"):
         if d[name] is not None:
             A.add(name, d[name].nbytes)
     for g0, nb in groups:
@@ -329,7 +348,7 @@ def test_eval_buffers(env, kind, B):
         if has_sum:
             A.add(f"tot{g0}", nb * 8)
     A.build()
-    for name in ("X", "y", "center", "scale", "codes", "eta_offset"):
+    for name in ("X", "y", "center", "scale", "codes", "eta_offset", "row_weight"):
         if d[name] is not None:
             A.put(name, d[name])
     got = np.empty((K, B))
@@ -347,9 +366,16 @@ def test_eval_buffers(env, kind, B):
         elif kind == "poisson":
             rc = env.lib.dlsa_poisson_loglik_batched_sum(A.ptr("X"), A.ptr("y"), *common, ll, ts,
                                                          env.stream)
-        elif kind == "poisson_offset":
+        elif kind.startswith("poisson_offset"):
             rc = env.lib.dlsa_poisson_loglik_batched_sum_offset(
                 A.ptr("X"), A.ptr("y"), A.ptr("eta_offset"), *common, ll, ts, env.stream)
+        elif kind == "logistic_weighted_nan_behind":
+            rc = env.lib.dlsa_logistic_loglik_batched_sum_weighted(
+                A.ptr("X"), A.ptr("y"), A.ptr("row_weight"), *common, ll, ts, env.stream)
+        elif kind == "poisson_weighted_nan_behind":
+            rc = env.lib.dlsa_poisson_loglik_batched_sum_weighted(
+                A.ptr("X"), A.ptr("y"), A.ptr("eta_offset"), A.ptr("row_weight"), *common, ll, ts,
+                env.stream)
         else:
             levels = np.asarray(d["levels"], dtype=np.int32)
             rc = env.lib.dlsa_logistic_loglik_categorical(
@@ -367,10 +393,15 @@ def test_eval_buffers(env, kind, B):
     ref = d["ref"]
     assert not got[2].view(np.uint64).any(), "the empty partition's row is not exactly 0"
     for k in range(K):
+        if k == nan_part:
+            assert np.isnan(got[k]).all(), "the partition that holds the NaN"
+            continue
         err, bound = np.abs(got[k] - ref[k]).max(), REL_LL * np.abs(ref[k]).max()
         print(f"{kind} B={B} partition {k}: max err {err:.3e} bound {bound:.3e}")
         assert err <= bound, k
-    if has_sum:
+    if has_sum and nan_part >= 0:
+        assert np.isnan(tot).all()
+    elif has_sum:
         rs = ref.sum(0)
         assert np.abs(tot - rs).max() <= REL_LL * np.abs(rs).max()
         acc = np.zeros(B)

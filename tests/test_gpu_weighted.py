@@ -277,7 +277,7 @@ BAD_SIZES = (1500, 2000, 2003)
 
 
 @pytest.mark.parametrize("hessian", ["mixed", "fp64"])
-@pytest.mark.parametrize("family", ["logistic", "poisson_offset"])
+@pytest.mark.parametrize("family", ["logistic", "poisson_offset", "poisson"])
 @pytest.mark.parametrize("bad,where", [(np.nan, "first"), (np.inf, "middle"), (-1.0, "last")])
 def test_bad_weight(M, family, bad, where, hessian):
     """The bad weight ends its partition NONFINITE with all-zero outputs; the
@@ -289,6 +289,9 @@ def test_bad_weight(M, family, bad, where, hessian):
     n = int(off[-1])
     if family == "logistic":
         X, y = O.simulate_counter(n, p, seed=5)
+        o = None
+    elif family == "poisson":  # the weighted kernels without the offset stream
+        X, y = G.simulate(n, p, seed=7, fit_intercept=fi)
         o = None
     else:
         X, y, o = G.simulate_offset(n, p, fit_intercept=fi)
@@ -305,7 +308,7 @@ def test_bad_weight(M, family, bad, where, hessian):
         if family == "logistic":
             return _abi_fit(M, "dlsa_logistic_fit_batched_weighted", X, y, off, fi, [wd], hessian)
         return _abi_fit(M, "dlsa_poisson_fit_batched_weighted", X, y, off, fi,
-                        [torch.from_numpy(o).cuda(), wd], hessian)
+                        [None if o is None else torch.from_numpy(o).cuda(), wd], hessian)
 
     rc, clean = run(w)
     assert rc == 0 and clean["status"].tolist() == [0, 0, 0]
