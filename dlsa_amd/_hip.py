@@ -131,6 +131,14 @@ SIGNATURES = {
         ctypes.c_int,
         [_P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _F64, _P, _P, _P, _P, _P, _P,
          ctypes.POINTER(FitOptions), _P]),
+    # the categorical entries with row_weight [n] inserted after y
+    "dlsa_logistic_loglik_categorical_weighted": (
+        ctypes.c_int,
+        [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "dlsa_logistic_fit_categorical_weighted": (
+        ctypes.c_int,
+        [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _F64, _P, _P, _P, _P, _P,
+         _P, ctypes.POINTER(FitOptions), _P]),
     "dlsa_partition_rows": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "dlsa_last_fit_stats": (ctypes.c_int, [ctypes.POINTER(FitStats)]),
     "dlsa_reduce_partitions": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P]),

@@ -189,9 +189,22 @@ int dlsa_logistic_fit_categorical(const double* Xn, const uint8_t* codes, const 
                                   double tol, double* theta, double* sig_inv,
                                   double* sig_inv_theta, double* loglik, int32_t* iters,
                                   int32_t* status, const dlsa_fit_options* opt, void* stream) {
-  return fit_categorical(Xn, codes, y, offsets, K, q, F, levels, fit_intercept, center, scale,
-                         max_iter, tol, {theta, sig_inv, sig_inv_theta, loglik, iters, status},
-                         opt, stream);
+  return fit_categorical(Xn, codes, y, nullptr, offsets, K, q, F, levels, fit_intercept, center,
+                         scale, max_iter, tol,
+                         {theta, sig_inv, sig_inv_theta, loglik, iters, status}, opt, stream);
+}
+
+int dlsa_logistic_fit_categorical_weighted(const double* Xn, const uint8_t* codes, const double* y,
+                                           const double* row_weight, const int64_t* offsets,
+                                           int32_t K, int32_t q, int32_t F, const int32_t* levels,
+                                           int32_t fit_intercept, const double* center,
+                                           const double* scale, int32_t max_iter, double tol,
+                                           double* theta, double* sig_inv, double* sig_inv_theta,
+                                           double* loglik, int32_t* iters, int32_t* status,
+                                           const dlsa_fit_options* opt, void* stream) {
+  return fit_categorical(Xn, codes, y, row_weight, offsets, K, q, F, levels, fit_intercept, center,
+                         scale, max_iter, tol,
+                         {theta, sig_inv, sig_inv_theta, loglik, iters, status}, opt, stream);
 }
 
 int dlsa_ols_fit_batched(const double* X, const double* y, const int64_t* offsets, int32_t K,
@@ -358,12 +371,13 @@ int dlsa_poisson_loglik_batched_sum_weighted(const double* X, const double* y,
                       eta_offset, row_weight);
 }
 
-int dlsa_logistic_loglik_categorical(const double* Xn, const uint8_t* codes, const double* y,
-                                     const int64_t* offsets, int32_t K, int32_t q, int32_t F,
-                                     const int32_t* levels, int32_t fit_intercept,
-                                     const double* center, const double* scale,
-                                     const double* betas, int32_t n_beta, int32_t rows_per_chunk,
-                                     double* loglik, double* loglik_sum, void* stream_) {
+// (row_weight: prior weights or null)
+static int loglik_categorical(const double* Xn, const uint8_t* codes, const double* y,
+                              const double* row_weight, const int64_t* offsets, int32_t K,
+                              int32_t q, int32_t F, const int32_t* levels, int32_t fit_intercept,
+                              const double* center, const double* scale, const double* betas,
+                              int32_t n_beta, int32_t rows_per_chunk, double* loglik,
+                              double* loglik_sum, void* stream_) {
   g_last_error.clear();
   hipStream_t stream = (hipStream_t)stream_;
   int rc = check_offsets(offsets, K);
@@ -383,7 +397,7 @@ int dlsa_logistic_loglik_categorical(const double* Xn, const uint8_t* codes, con
     set_error("null Xn, codes or y");
     return DLSA_E_INVALID;
   }
-  EvalCatArgs ea;
+  EvalCatArgsWgt ea;  // (the unweighted kernels take its EvalCatArgs slice)
   memset(&ea, 0, sizeof(ea));
   ea.q = q;
   ea.F = F;
@@ -395,7 +409,7 @@ int dlsa_logistic_loglik_categorical(const double* Xn, const uint8_t* codes, con
     ea.toff[f] = o;
     o += levels[f];
   }
-  if (!eval_cat_plan(ea)) {
+  if (!eval_cat_plan(ea, row_weight != nullptr)) {
     set_error("categorical evaluation: the coefficient table does not fit the LDS");
     return DLSA_E_UNSUPPORTED;
   }
@@ -435,6 +449,8 @@ int dlsa_logistic_loglik_categorical(const double* Xn, const uint8_t* codes, con
       ea.c_hi = (uintptr_t)(codes + n_total * (int64_t)F) & ~(uintptr_t)15;
     }
     ea.y_last4 = (uintptr_t)(y + n_total) - 4;
+    ea.row_weight = row_weight;
+    if (row_weight) ea.w_last4 = (uintptr_t)(row_weight + n_total) - 4;
     DLSA_HIP_TRY(launch_loglik_cat(ea, pl.n_chunks, stream));
     DLSA_HIP_TRY(hipMemcpyAsync(h_bad.data(), d_bad, 4LL * pl.n_chunks, hipMemcpyDeviceToHost,
                                 stream));
@@ -452,6 +468,30 @@ int dlsa_logistic_loglik_categorical(const double* Xn, const uint8_t* codes, con
     }
   }
   return DLSA_OK;
+}
+
+int dlsa_logistic_loglik_categorical(const double* Xn, const uint8_t* codes, const double* y,
+                                     const int64_t* offsets, int32_t K, int32_t q, int32_t F,
+                                     const int32_t* levels, int32_t fit_intercept,
+                                     const double* center, const double* scale,
+                                     const double* betas, int32_t n_beta, int32_t rows_per_chunk,
+                                     double* loglik, double* loglik_sum, void* stream) {
+  return loglik_categorical(Xn, codes, y, nullptr, offsets, K, q, F, levels, fit_intercept,
+                            center, scale, betas, n_beta, rows_per_chunk, loglik, loglik_sum,
+                            stream);
+}
+
+int dlsa_logistic_loglik_categorical_weighted(const double* Xn, const uint8_t* codes,
+                                              const double* y, const double* row_weight,
+                                              const int64_t* offsets, int32_t K, int32_t q,
+                                              int32_t F, const int32_t* levels,
+                                              int32_t fit_intercept, const double* center,
+                                              const double* scale, const double* betas,
+                                              int32_t n_beta, int32_t rows_per_chunk,
+                                              double* loglik, double* loglik_sum, void* stream) {
+  return loglik_categorical(Xn, codes, y, row_weight, offsets, K, q, F, levels, fit_intercept,
+                            center, scale, betas, n_beta, rows_per_chunk, loglik, loglik_sum,
+                            stream);
 }
 
 int dlsa_partition_rows(const int32_t* part_id, int64_t n, int32_t K, int32_t n_arrays,

@@ -509,6 +509,17 @@ struct CatArgs {
   // gradient residuals, [2 + i] w x_i of numeric column i)
   const double* hscale;
 };
+// CatArgs of the weighted instantiations (cat_pass_wgt.hip): every row's w,
+// residual and log-likelihood term are multiplied by row_weight.  The
+// unweighted kernels keep CatArgs (and its size: DESIGN 4.5e).
+struct CatArgsWgt : CatArgs {
+  const double* row_weight;  // [n_total] prior weights omega
+  double* wmax;              // [n_chunks] the presence pass's max finite omega per chunk
+};
+template <bool WGT>
+struct cat_args_of {
+  typedef typename std::conditional<WGT, CatArgsWgt, CatArgs>::type type;
+};
 
 // Log-likelihood evaluation pass on the categorical-code layout
 // (eval_cat_pass.hip): P <= DLSA_MAX_P, the other limits are the fit's.
@@ -532,8 +543,16 @@ struct EvalCatArgs {
   int32_t levels[kCatMaxFactors];
   int32_t toff[kCatMaxFactors];  // first table entry of factor f: sum of levels[0..f)
 };
-bool eval_cat_plan(EvalCatArgs& a);  // sets rb and nslot; false: does not fit the LDS
-hipError_t launch_loglik_cat(const EvalCatArgs& a, int n_chunks, hipStream_t s);
+// EvalCatArgs of the weighted kernels: every row's term is multiplied by
+// row_weight, one more 256-byte-piece stream behind y in the ring slot
+struct EvalCatArgsWgt : EvalCatArgs {
+  const double* row_weight;  // [n_total] or null (the unweighted kernels, which take EvalCatArgs)
+  uintptr_t w_last4;         // last 4-B address inside row_weight
+};
+// sets rb and nslot (weighted: the ring slot also holds omega); false: does not fit the LDS
+bool eval_cat_plan(EvalCatArgs& a, bool weighted = false);
+// routes on a.row_weight; the unweighted kernels are handed the EvalCatArgs slice
+hipError_t launch_loglik_cat(const EvalCatArgsWgt& a, int n_chunks, hipStream_t s);
 hipError_t launch_loglik_total(const double* ll, int K, int B, double* out, hipStream_t s);
 
 // Row repartitioning (partition_rows.hip): stable counting sort by partition id.
@@ -561,6 +580,13 @@ hipError_t launch_cat_presence(const CatArgs& a, int n_chunks, int32_t* counts, 
 hipError_t launch_cat_mark(const CatArgs& a, const int32_t* pcb, const int32_t* counts,
                            const int32_t* bad, int K, int32_t* phase, int32_t* status,
                            int32_t* bad_part, hipStream_t s);
+// with prior weights (cat_pass_wgt.hip): the pass, and the presence pass whose
+// level flags count rows with omega > 0 only and which also clears and fills
+// a.wmax [n_chunks]
+hipError_t launch_cat_pass_wgt(const CatArgsWgt& a, bool standardize, int n_chunks,
+                               hipStream_t s);
+hipError_t launch_cat_presence_wgt(const CatArgsWgt& a, int n_chunks, int32_t* counts,
+                                   int32_t* bad, double* colmax, hipStream_t s);
 hipError_t launch_wide_row(const WideArgs& a, bool standardize, int family, int n_chunks,
                            hipStream_t s);
 hipError_t launch_wide_gram(const WideArgs& a, bool standardize, hipStream_t s);

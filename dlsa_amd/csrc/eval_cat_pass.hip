@@ -13,6 +13,12 @@
 // a row's lookup is branch-free and its BP candidates are contiguous 16-byte
 // reads.  Each chunk writes one partial per candidate and its count of codes
 // >= levels[f] (looked up as code 0); no atomics.
+//
+// WGT: prior weights, ll[k, b] = sum_i omega_i l_ib.  omega is one more stream
+// travelling like y: 256-byte pieces behind y in the ring slot, clamped to the
+// buffer by w_last4.  The row's term is multiplied by omega and added only for
+// a valid row: the rows of a chunk's last block past its end hold the next
+// partition's omega, whatever it is.  The weights are not checked here.
 #include "dlsa_internal.hpp"
 #include "glm_row.hpp"
 
@@ -24,15 +30,16 @@ constexpr int CW = 4;  // waves
 
 // 1 KiB pieces (64 lanes x 16 B) that cover `bytes` from any start inside a
 // 16-byte granule
-__host__ __device__ __forceinline__ int ec_pieces16(int bytes) {
+__host__ __device__ constexpr int ec_pieces16(int bytes) {
   return bytes > 0 ? (bytes + 16 + 1023) / 1024 : 0;
 }
 
 struct EcGeom {
   int npx, dx, npc, dc, npy, dy;  // pieces of a block and pieces per wave: X, codes, y
   int c_off, y_off, slot_bytes;
+  int npw, dw, w_off;  // omega (wgt), pieced like y
 };
-__host__ __device__ __forceinline__ EcGeom ec_geom(int RB, int q, int F) {
+__host__ __device__ __forceinline__ EcGeom ec_geom(int RB, int q, int F, bool wgt) {
   EcGeom g;
   g.npx = ec_pieces16(RB * q * 8);
   g.dx = (g.npx + CW - 1) / CW;
@@ -42,7 +49,10 @@ __host__ __device__ __forceinline__ EcGeom ec_geom(int RB, int q, int F) {
   g.dy = (g.npy + CW - 1) / CW;
   g.c_off = g.dx * CW * 1024;
   g.y_off = g.c_off + g.dc * CW * 1024;
-  g.slot_bytes = g.y_off + g.dy * CW * 256;
+  g.npw = wgt ? RB / 32 : 0;
+  g.dw = (g.npw + CW - 1) / CW;
+  g.w_off = g.y_off + g.dy * CW * 256;
+  g.slot_bytes = g.w_off + g.dw * CW * 256;
   return g;
 }
 
@@ -54,8 +64,29 @@ __host__ __device__ __forceinline__ int ec_table_doubles(int entries, int q, int
   return entries * BP + (q + 1) * BP + 2 * (q + 1) + CW * kEvalCatMaxB;
 }
 
-template <int BP>
-__global__ __launch_bounds__(256) void loglik_cat_kernel(const EvalCatArgs a) {
+template <bool WGT>
+struct ec_args_of {
+  typedef typename std::conditional<WGT, EvalCatArgsWgt, EvalCatArgs>::type type;
+};
+
+// Outstanding loads against the vmcnt waits.  A wave issues per block
+//   per_blk = dx + dc + dy + dw
+// loads, at most 9 + 2 + 2 + 2 at RB = 256, q = 16, F = 16 (33 1-KiB pieces of
+// X and 5 of codes, 8 256-B pieces of y and 8 of omega, each over CW waves).
+// When it waits for the oldest block, (nslot - 1) per_blk loads are in flight
+// and (nslot - 2) per_blk are kept; nslot <= 4 (eval_cat_plan).  Both stay
+// inside the 6-bit counter, and the kept count inside wait_vmcnt_le<40>.
+constexpr int ec_ceil(int a, int b) { return (a + b - 1) / b; }
+constexpr int kEcMaxPerBlk = ec_ceil(ec_pieces16(256 * kCatQMax * 8), CW) +
+                             ec_ceil(ec_pieces16(256 * kCatMaxFactors), CW) +
+                             2 * ec_ceil(256 / 32, CW);
+constexpr int kEcMaxSlots = 4;
+static_assert(kEcMaxPerBlk == 15, "per-block loads of a wave");
+static_assert((kEcMaxSlots - 1) * kEcMaxPerBlk < 64, "loads in flight fit vmcnt (6 bits)");
+static_assert((kEcMaxSlots - 2) * kEcMaxPerBlk <= 40, "kept loads fit wait_vmcnt_le<40>");
+
+template <int BP, bool WGT>
+__global__ __launch_bounds__(256) void loglik_cat_kernel(const typename ec_args_of<WGT>::type a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int chunk = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -65,7 +96,7 @@ __global__ __launch_bounds__(256) void loglik_cat_kernel(const EvalCatArgs a) {
   const int nrows = a.chunk_rows[chunk];
   const int nb = (nrows + RB - 1) / RB;
   const int nslot = a.nslot;
-  const EcGeom g = ec_geom(RB, q, F);
+  const EcGeom g = ec_geom(RB, q, F, WGT);
   const int E = ec_entries(a);
 
   double* T = (double*)(smem + nslot * g.slot_bytes);  // [E][BP]
@@ -139,8 +170,19 @@ __global__ __launch_bounds__(256) void loglik_cat_kernel(const EvalCatArgs a) {
       __builtin_amdgcn_global_load_lds((gbl_void_t*)src,
                                        (lds_void_t*)(sbase + g.y_off + j * 256), 4, 0, 0);
     }
+    if constexpr (WGT) {
+      for (int i = 0; i < g.dw; ++i) {
+        const int j = wid + CW * i;
+        const int jj = j < g.npw ? j : g.npw - 1;
+        uintptr_t src = (uintptr_t)(a.row_weight + r) + (uintptr_t)jj * 256 + (uintptr_t)lane * 4;
+        src = src < a.w_last4 ? src : a.w_last4;
+        __builtin_amdgcn_global_load_lds((gbl_void_t*)src,
+                                         (lds_void_t*)(sbase + g.w_off + j * 256), 4, 0, 0);
+      }
+    }
   };
-  const int per_blk = (xdma ? g.dx : 0) + (cdma ? g.dc : 0) + g.dy;  // loads per wave and block
+  // loads per wave and block
+  const int per_blk = (xdma ? g.dx : 0) + (cdma ? g.dc : 0) + g.dy + (WGT ? g.dw : 0);
 
   double llacc[BP];
 #pragma unroll
@@ -196,11 +238,13 @@ __global__ __launch_bounds__(256) void loglik_cat_kernel(const EvalCatArgs a) {
       }
     }
     const double yv = ((const double*)(slot + g.y_off))[rt];
+    double om = 1.0;  // (the literal 1 without weights)
+    if constexpr (WGT) om = ((const double*)(slot + g.w_off))[rt];
 #pragma unroll
     for (int b = 0; b < BP; ++b) {
       if (b < B) {
         const double e = eta[b];
-        if (valid) llacc[b] += row_loglik<FAMILY_LOGISTIC>(e, yv, 1.0, 0.0);
+        if (valid) llacc[b] += row_loglik<FAMILY_LOGISTIC>(e, yv, om, 0.0);
       }
     }
   }
@@ -231,12 +275,23 @@ __global__ __launch_bounds__(256) void loglik_cat_kernel(const EvalCatArgs a) {
 
 constexpr int kEcStaticLds = 4 * (2 * kCatMaxFactors + CW);
 
-template <int BP>
-hipError_t ec_launch(const EvalCatArgs& a, int n_chunks, size_t lds, hipStream_t s) {
-  hipError_t e = ensure_max_lds((const void*)loglik_cat_kernel<BP>, 160 * 1024 - 1024);
+template <int BP, bool WGT>
+hipError_t ec_launch(const typename ec_args_of<WGT>::type& a, int n_chunks, size_t lds,
+                     hipStream_t s) {
+  hipError_t e = ensure_max_lds((const void*)loglik_cat_kernel<BP, WGT>, 160 * 1024 - 1024);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(loglik_cat_kernel<BP>, dim3(n_chunks), dim3(256), lds, s, a);
+  hipLaunchKernelGGL((loglik_cat_kernel<BP, WGT>), dim3(n_chunks), dim3(256), lds, s, a);
   return hipGetLastError();
+}
+template <bool WGT>
+hipError_t ec_launch_bp(const typename ec_args_of<WGT>::type& a, int BP, int n_chunks, size_t lds,
+                        hipStream_t s) {
+  switch (BP) {
+    case 2: return ec_launch<2, WGT>(a, n_chunks, lds, s);
+    case 4: return ec_launch<4, WGT>(a, n_chunks, lds, s);
+    case 8: return ec_launch<8, WGT>(a, n_chunks, lds, s);
+    default: return ec_launch<16, WGT>(a, n_chunks, lds, s);
+  }
 }
 
 int ec_bp(int B) { return B <= 2 ? 2 : B <= 4 ? 4 : B <= 8 ? 8 : 16; }
@@ -247,32 +302,29 @@ int ec_bp(int B) { return B <= 2 ? 2 : B <= 4 ? 4 : B <= 8 ? 8 : 16; }
 // the workgroup's LDS beside the tables; up to 4 slots while the workgroup
 // stays within half a CU's LDS (two workgroups per CU: the pass is bound by
 // the fp64 exp / log1p of every row and candidate, not only by HBM).
-bool eval_cat_plan(EvalCatArgs& a) {
+bool eval_cat_plan(EvalCatArgs& a, bool weighted) {
   const int BP = ec_bp(a.nbeta);
   const int fixed = ec_table_doubles(ec_entries(a), a.q, BP) * 8 + kEcStaticLds;
   const int cap = 160 * 1024 - 1024;
   for (int RB : {256, 128, 64}) {
-    const int slot = ec_geom(RB, a.q, a.F).slot_bytes;
+    const int slot = ec_geom(RB, a.q, a.F, weighted).slot_bytes;
     if (fixed + 2 * slot > cap) continue;
     a.rb = RB;
     int n = 2;
-    while (n < 4 && fixed + (n + 1) * slot <= cap / 2) ++n;
+    while (n < kEcMaxSlots && fixed + (n + 1) * slot <= cap / 2) ++n;
     a.nslot = n;
     return true;
   }
   return false;
 }
 
-hipError_t launch_loglik_cat(const EvalCatArgs& a, int n_chunks, hipStream_t s) {
+hipError_t launch_loglik_cat(const EvalCatArgsWgt& a, int n_chunks, hipStream_t s) {
   const int BP = ec_bp(a.nbeta);
-  const size_t lds = (size_t)a.nslot * ec_geom(a.rb, a.q, a.F).slot_bytes +
+  const bool wgt = a.row_weight != nullptr;
+  const size_t lds = (size_t)a.nslot * ec_geom(a.rb, a.q, a.F, wgt).slot_bytes +
                      (size_t)ec_table_doubles(ec_entries(a), a.q, BP) * 8;
-  switch (BP) {
-    case 2: return ec_launch<2>(a, n_chunks, lds, s);
-    case 4: return ec_launch<4>(a, n_chunks, lds, s);
-    case 8: return ec_launch<8>(a, n_chunks, lds, s);
-    default: return ec_launch<16>(a, n_chunks, lds, s);
-  }
+  return wgt ? ec_launch_bp<true>(a, BP, n_chunks, lds, s)
+             : ec_launch_bp<false>(a, BP, n_chunks, lds, s);
 }
 
 // total[b] = sum_k ll[k, b] in k order: the group-by sum of model_eval.py:38

@@ -2,7 +2,10 @@
 // codes per row.  Every pass is exact (PHASE_F64); a presence pass over all
 // rows comes first (missing levels, invalid codes, the fixed-point grids of
 // the histograms).  The Newton solve, the warm-start levels and the phases are
-// the fused path's.
+// the fused path's.  With prior weights (row_weight) the pre-pass of the dense
+// weighted fits decides NONFINITE / SINGULAR first, the presence pass counts a
+// level only in rows with omega > 0 and takes the partition's omega_max, which
+// scales the grids, and the passes are cat_pass_wgt.hip's.
 #include "fit_driver.hpp"
 
 namespace dlsa {
@@ -17,9 +20,17 @@ namespace {
 // outlier row coarsens only its own partition's grid.  colmax
 // [n_chunks][kCatQMax] is the presence pass's max |x_i| per chunk and column;
 // hc / hs are the host's center and scale (0 / 1 without standardisation).
+// Prior weights: every term carries omega, so each bound is multiplied by the
+// partition's omega_max = the max over its chunks of wmax [n_chunks] (the
+// presence pass's largest finite omega; empty without weights, and 0 -- a
+// partition the pre-pass has ended -- counts as 1).  The residual bound then
+// assumes 0 <= y <= 1, as the unweighted grid does.  omega == 1 gives the
+// unweighted grids; a huge weight coarsens only its own partition's bins,
+// which are then resolved omega_max / mean omega times coarser relative to
+// their own sums than the unweighted ~1e-13.
 std::vector<double> cat_grids(const std::vector<Plan>& plans, int K, int q, bool standardize,
-                              const std::vector<double>& colmax, const std::vector<double>& hc,
-                              const std::vector<double>& hs) {
+                              const std::vector<double>& colmax, const std::vector<double>& wmax,
+                              const std::vector<double>& hc, const std::vector<double>& hs) {
   const Plan& pl = plans.back();
   int64_t rmax = 1024;
   for (const Plan& qn : plans) rmax = std::max<int64_t>(rmax, qn.max_chunk_rows);
@@ -31,14 +42,19 @@ std::vector<double> cat_grids(const std::vector<Plan>& plans, int K, int q, bool
   std::vector<double> grids((size_t)K * (kCatQMax + 2), 1.0);
   for (int k = 0; k < K; ++k) {
     double* o = grids.data() + (size_t)k * (kCatQMax + 2);
-    o[0] = grid(0.25);  // w = mu (1 - mu) <= 1/4; pair cells
-    o[1] = grid(1.0);   // |y - mu| <= 1
+    double om = 0.0;
+    if (!wmax.empty())
+      for (int c = pl.part_chunk_begin[k]; c < pl.part_chunk_begin[k + 1]; ++c)
+        om = std::max(om, wmax[c]);
+    if (!(om > 0) || !std::isfinite(om)) om = 1.0;
+    o[0] = grid(0.25 * om);  // omega w, w = mu (1 - mu) <= 1/4; pair cells
+    o[1] = grid(om);         // omega |y - mu| <= omega
     for (int j = 0; j < q; ++j) {
       double m = 0.0;
       for (int c = pl.part_chunk_begin[k]; c < pl.part_chunk_begin[k + 1]; ++c)
         m = std::max(m, colmax[(size_t)c * kCatQMax + j]);
       if (standardize) m = (m + std::fabs(hc[j])) / std::fabs(hs[j]);  // the kernel sums w (x - c) / s
-      o[2 + j] = grid(0.25 * m);
+      o[2 + j] = grid(0.25 * om * m);
     }
   }
   return grids;
@@ -47,8 +63,8 @@ std::vector<double> cat_grids(const std::vector<Plan>& plans, int K, int q, bool
 }  // namespace
 
 int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
-                    const int64_t* offsets, int32_t K, int32_t q, int32_t F,
-                    const int32_t* levels, int32_t fit_intercept, const double* center,
+                    const double* row_weight, const int64_t* offsets, int32_t K, int32_t q,
+                    int32_t F, const int32_t* levels, int32_t fit_intercept, const double* center,
                     const double* scale, int32_t max_iter, double tol, const FitOutputs& out,
                     const dlsa_fit_options* opt_in, void* stream_) {
   const FitStart start = fit_begin(opt_in, stream_);
@@ -67,7 +83,7 @@ int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
     return DLSA_E_INVALID;
   }
 
-  CatArgs ca;
+  CatArgsWgt ca;  // (the unweighted kernels take its CatArgs slice)
   memset(&ca, 0, sizeof(ca));
   ca.q = q;
   ca.F = F;
@@ -120,6 +136,7 @@ int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
   const int64_t off_badp = b.take(4LL * K);
   const int64_t off_colmax = b.take(8LL * kCatQMax * nc);
   const int64_t off_hs = b.take(8LL * (kCatQMax + 2) * K);
+  const int64_t off_wmax = row_weight ? b.take(8 * nc) : 0;  // weighted fits only
   g_stats.n_chunks = pl.n_chunks;
 
   Workspace ws(stream);
@@ -155,10 +172,18 @@ int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
   sa.NT = pl.NT;
   sa.escalate_to = PHASE_F64;  // every categorical pass is exact
   DLSA_HIP_TRY(fit_init(sa, d_offsets, K, PHASE_F64, stream));
+  // prior weights: a negative or non-finite omega ends its partition
+  // NONFINITE, sum omega = 0 SINGULAR, before the presence pass marks missing
+  // levels among the partitions still running
+  if (row_weight)
+    DLSA_HIP_TRY(launch_fit_prepass(FAMILY_LOGISTIC, y, nullptr, row_weight, d_offsets, K, P, ic,
+                                    out.theta, nullptr, sa.phase, out.status, stream));
 
   ca.Xn = Xn;
   ca.codes = codes;
   ca.y = y;
+  ca.row_weight = row_weight;
+  ca.wmax = row_weight ? (double*)ws.at(off_wmax) : nullptr;
   ca.chunk_row0 = (const int64_t*)ws.at(L.off_row0);
   ca.chunk_rows = (const int32_t*)ws.at(L.off_rows);
   ca.chunk_part = (const int32_t*)ws.at(L.off_part);
@@ -179,8 +204,16 @@ int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
   if (!h.init(K)) return DLSA_E_HIP;
   std::vector<int32_t> h_badp(K, 0);
   std::vector<double> h_colmax((size_t)kCatQMax * nc, 0.0);
+  std::vector<double> h_wmax(row_weight ? (size_t)nc : 0, 0.0);
   DLSA_HIP_TRY(upload(pl));
-  DLSA_HIP_TRY(launch_cat_presence(ca, pl.n_chunks, d_counts, d_bad, d_colmax, stream));
+  if (row_weight) {
+    DLSA_HIP_TRY(launch_cat_presence_wgt(ca, pl.n_chunks, d_counts, d_bad, d_colmax, stream));
+    if (pl.n_chunks > 0)
+      DLSA_HIP_TRY(hipMemcpyAsync(h_wmax.data(), ca.wmax, 8LL * pl.n_chunks,
+                                  hipMemcpyDeviceToHost, stream));
+  } else {
+    DLSA_HIP_TRY(launch_cat_presence(ca, pl.n_chunks, d_counts, d_bad, d_colmax, stream));
+  }
   if (pl.n_chunks > 0)
     DLSA_HIP_TRY(hipMemcpyAsync(h_colmax.data(), d_colmax, 8LL * kCatQMax * pl.n_chunks,
                                 hipMemcpyDeviceToHost, stream));
@@ -196,7 +229,8 @@ int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
     DLSA_HIP_TRY(hipMemcpy(hs.data(), scale, 8LL * q, hipMemcpyDeviceToHost));
   }
   // (staged into the pinned arena on upload)
-  const std::vector<double> h_hs = cat_grids(plans, K, q, center != nullptr, h_colmax, hc, hs);
+  const std::vector<double> h_hs =
+      cat_grids(plans, K, q, center != nullptr, h_colmax, h_wmax, hc, hs);
   DLSA_HIP_TRY(staged_upload(d_hs, h_hs.data(), 8LL * (kCatQMax + 2) * K, stream));
   ca.hscale = d_hs;
   for (int k = 0; k < K; ++k)
@@ -213,8 +247,10 @@ int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
   const bool trace = trace_enabled();
   auto pass_and_solve = [&](const Plan& qn, const std::vector<int64_t>& part_rows,
                             bool clear_counters) -> hipError_t {
-    hipError_t e = timed(&g_stats.ms_pass_fp64,
-                         [&] { return launch_cat_pass(ca, standardize, qn.n_chunks, stream); });
+    hipError_t e = timed(&g_stats.ms_pass_fp64, [&] {
+      return row_weight ? launch_cat_pass_wgt(ca, standardize, qn.n_chunks, stream)
+                        : launch_cat_pass(ca, standardize, qn.n_chunks, stream);
+    });
     g_stats.passes_fp64++;
     g_stats.rows_fp64 += phase_rows(part_rows, h.phase, PHASE_F64);
     if (e == hipSuccess && clear_counters) e = hipMemsetAsync(sa.counters, 0, 16, stream);

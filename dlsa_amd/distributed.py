@@ -98,15 +98,13 @@ def loglik_sharded(X, y, offsets, betas, fit_intercept=False, center=None, scale
     this rank's partitions on the device; ONE all-reduce of those B doubles
     gives every rank the global sums.  Returns a numpy [B] array.
     ``sample_weight``: the prior weights of the local shard's rows
-    (``logistic_loglik_batched``; dense layout only)."""
+    (``logistic_loglik_batched`` / ``logistic_loglik_batched_categorical``)."""
     from .models import logistic_loglik_batched, logistic_loglik_batched_categorical
 
-    if codes is not None and sample_weight is not None:
-        raise ValueError("sample_weight runs on the dense layout only (no codes)")
     if codes is not None:
         _, tot = logistic_loglik_batched_categorical(
             X, codes, y, offsets, levels, betas, fit_intercept=fit_intercept, center=center,
-            scale=scale, return_sum=True)
+            scale=scale, return_sum=True, sample_weight=sample_weight)
     else:
         _, tot = logistic_loglik_batched(X, y, offsets, betas, fit_intercept=fit_intercept,
                                          center=center, scale=scale, return_sum=True,
@@ -130,13 +128,15 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
     of the local shard's rows (``poisson_model_batched_offset``); the combine
     step never sees it.
     ``sample_weight``: per-row prior weights of the local shard's rows
-    (``logistic_model_batched_weighted`` / ``poisson_model_batched_weighted``;
-    dense layout only).  N, the DBIC's sample size, stays the ROW count: weights that are
+    (``logistic_model_batched_weighted`` / ``poisson_model_batched_weighted``,
+    with ``codes`` ``logistic_model_batched_categorical_weighted``).  N, the
+    DBIC's sample size, stays the ROW count: weights that are
     precision or survey weights leave the number of observations unchanged.  A
     frequency-weights user who wants N = sum of the weights calls
     ``finish(..., n_global=)`` on the reduced sums directly.
     """
     from .models import (logistic_model_batched, logistic_model_batched_categorical,
+                         logistic_model_batched_categorical_weighted,
                          logistic_model_batched_weighted, poisson_model_batched,
                          poisson_model_batched_offset, poisson_model_batched_weighted)
 
@@ -145,12 +145,16 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
     if (eta_offset is not None or exposure is not None) and family != "poisson":
         raise ValueError("eta_offset / exposure need family='poisson'")
     if sample_weight is not None:  # (None: exactly the unweighted calls below)
-        if codes is not None:
-            raise ValueError("sample_weight runs on the dense layout only (no codes)")
         if family == "poisson":
+            if codes is not None:
+                raise ValueError("family='poisson' runs on the dense layout only (no codes)")
             fit = poisson_model_batched_weighted(X, y, offsets, sample_weight=sample_weight,
                                                  eta_offset=eta_offset, exposure=exposure,
                                                  fit_intercept=fit_intercept, **fit_kw)
+        elif codes is not None:
+            fit = logistic_model_batched_categorical_weighted(
+                X, codes, y, offsets, levels, sample_weight=sample_weight,
+                fit_intercept=fit_intercept, **fit_kw)
         else:
             fit = logistic_model_batched_weighted(X, y, offsets, sample_weight=sample_weight,
                                                   fit_intercept=fit_intercept, **fit_kw)

@@ -600,9 +600,35 @@ def logistic_model_batched_categorical(Xn, codes, y, offsets, levels, fit_interc
     a factor value outside dummy_info, ``read_csv_partitioned``'s
     ``zero_partitions``: the reference's column-set check fails there too,
     models.py:84-91)."""
+    return logistic_model_batched_categorical_weighted(
+        Xn, codes, y, offsets, levels, None, fit_intercept, center, scale, max_iter, tol,
+        record_timing, rows_per_chunk, zero_partitions, device)
+
+
+def logistic_model_batched_categorical_weighted(Xn, codes, y, offsets, levels, sample_weight=None,
+                                                fit_intercept=False, center=None, scale=None,
+                                                max_iter=100, tol=1e-10, record_timing=False,
+                                                rows_per_chunk=0, zero_partitions=None,
+                                                device=None):
+    """``logistic_model_batched_categorical`` with per-row prior weights.
+
+    ``sample_weight`` [n] (None: exactly the unweighted call): prior weights
+    omega, finite and >= 0 (``ValueError`` otherwise, or for a wrong length),
+    with the semantics of ``logistic_model_batched_weighted`` on the
+    dummy-expanded design.  The canonical use is a design made of factors
+    collapsed to its distinct cells: rows (cell, s successes, m trials) with
+    y = s / m and omega = m give the MLE and Sig_inv of the replicated 0/1
+    rows.  omega = 0 drops a row: a dummy column whose rows all have omega = 0
+    makes the partition "missing_level"; a negative or non-finite weight met on
+    the device "nonfinite", weights that sum to 0 "singular"
+    (``dlsa_logistic_fit_categorical_weighted``)."""
+    _check_row_extras(Xn, False, None, None, sample_weight)
     dev = _require_gpu(device)
     Xd, cd8, yd, offs, lv, cen, sca = _cat_inputs(Xn, codes, y, offsets, levels, center, scale,
                                                   dev)
+    entry, extras = _entry_and_extras("dlsa_logistic_fit_categorical",
+                                      "dlsa_logistic_fit_categorical_weighted", False, None, None,
+                                      sample_weight, dev)
     q, F, K = Xd.shape[1], cd8.shape[1], offs.size - 1
     P = int(bool(fit_intercept)) + q + int((lv - 1).sum())
     theta, sig, sigt, ll, iters, status = _alloc_outputs(K, P, dev)
@@ -610,12 +636,13 @@ def logistic_model_batched_categorical(Xn, codes, y, offsets, levels, fit_interc
     opt = _hip.default_options()
     opt.record_timing = 1 if record_timing else 0
     opt.rows_per_chunk = int(rows_per_chunk)
-    rc = lib.dlsa_logistic_fit_categorical(
-        _ptr(Xd), _ptr(cd8), _ptr(yd), offs.ctypes.data_as(ctypes.c_void_p), K, q, F,
+    rc = getattr(lib, entry)(
+        _ptr(Xd), _ptr(cd8), _ptr(yd), *map(_ptr, extras), offs.ctypes.data_as(ctypes.c_void_p),
+        K, q, F,
         lv.ctypes.data_as(ctypes.c_void_p), int(bool(fit_intercept)), _ptr(cen), _ptr(sca),
         int(max_iter), float(tol), _ptr(theta), _ptr(sig), _ptr(sigt), _ptr(ll), _ptr(iters),
         _ptr(status), ctypes.byref(opt), _stream(dev))
-    _hip.check(rc, "dlsa_logistic_fit_categorical")
+    _hip.check(rc, entry)
     stats = _hip.last_fit_stats()
     if zero_partitions is not None and len(zero_partitions):
         idx = torch.as_tensor(np.asarray(zero_partitions, dtype=np.int64), device=dev)
@@ -754,7 +781,7 @@ def poisson_loglik_batched_weighted(X, y, offsets, betas, sample_weight=None, et
 
 def logistic_loglik_batched_categorical(Xn, codes, y, offsets, levels, betas, fit_intercept=False,
                                         center=None, scale=None, rows_per_chunk=0, device=None,
-                                        return_sum=False):
+                                        return_sum=False, sample_weight=None):
     """``logistic_loglik_batched`` on the categorical-code layout of
     ``logistic_model_batched_categorical`` (same Xn / codes / levels / center /
     scale and parameter order): the log-likelihood of the dummy-expanded design
@@ -762,19 +789,27 @@ def logistic_loglik_batched_categorical(Xn, codes, y, offsets, levels, betas, fi
     table in LDS (``dlsa_logistic_loglik_categorical``).  betas: [B, P]; more
     than 16 candidates are evaluated 16 to a pass.  Returns a [K, B] fp64
     device tensor, with ``return_sum`` also its [B] sum over the partitions.
-    A code >= levels[f] raises ``DlsaHipError``."""
+    A code >= levels[f] raises ``DlsaHipError``.  ``sample_weight`` [n] (None:
+    exactly the unweighted call): every row's term is multiplied by its prior
+    weight (finite and >= 0, n entries, else ``ValueError``), the
+    log-likelihood of ``logistic_model_batched_categorical_weighted``
+    (``dlsa_logistic_loglik_categorical_weighted``)."""
+    _check_row_extras(Xn, False, None, None, sample_weight)
     dev = _require_gpu(device)
     Xd, cd8, yd, offs, lv, cen, sca = _cat_inputs(Xn, codes, y, offsets, levels, center, scale,
                                                   dev)
+    entry, extras = _entry_and_extras("dlsa_logistic_loglik_categorical",
+                                      "dlsa_logistic_loglik_categorical_weighted", False, None,
+                                      None, sample_weight, dev)
     q, F, K = Xd.shape[1], cd8.shape[1], offs.size - 1
-    lib = _hip.load()
+    fn = getattr(_hip.load(), entry)
 
     def call(bd, g, out, total):
-        rc = lib.dlsa_logistic_loglik_categorical(
-            _ptr(Xd), _ptr(cd8), _ptr(yd), offs.ctypes.data_as(ctypes.c_void_p), K, q, F,
-            lv.ctypes.data_as(ctypes.c_void_p), int(bool(fit_intercept)), _ptr(cen), _ptr(sca),
-            _ptr(bd), g, int(rows_per_chunk), _ptr(out), _ptr(total), _stream(dev))
-        _hip.check(rc, "dlsa_logistic_loglik_categorical")
+        rc = fn(_ptr(Xd), _ptr(cd8), _ptr(yd), *map(_ptr, extras),
+                offs.ctypes.data_as(ctypes.c_void_p), K, q, F,
+                lv.ctypes.data_as(ctypes.c_void_p), int(bool(fit_intercept)), _ptr(cen), _ptr(sca),
+                _ptr(bd), g, int(rows_per_chunk), _ptr(out), _ptr(total), _stream(dev))
+        _hip.check(rc, entry)
 
     P = int(bool(fit_intercept)) + q + int((lv - 1).sum())
     return _loglik_groups(call, betas, P, K, dev, return_sum)

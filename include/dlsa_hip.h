@@ -343,11 +343,12 @@ int dlsa_poisson_loglik_batched_sum_offset(const double* X, const double* y,
  * (log(sum omega y / sum omega exp(eta_offset)), 0, ..., 0), the MLE of the
  * weighted intercept-only model, to which restarts go back.
  * Limits (each a follow-up):
- *   - the fused path on the dense layout only: P = p + intercept <=
- *     DLSA_MAX_P_FUSED (192), else DLSA_E_UNSUPPORTED before any launch (no
- *     weighted wide path);
- *   - no weights on the categorical layout (dlsa_logistic_fit_categorical) nor
- *     for OLS (dlsa_ols_fit_batched);
+ *   - the fused path only: P = p + intercept <= DLSA_MAX_P_FUSED (192), else
+ *     DLSA_E_UNSUPPORTED before any launch (no weighted wide path);
+ *   - the categorical-code layout takes weights through entries of its own,
+ *     dlsa_logistic_fit_categorical_weighted and
+ *     dlsa_logistic_loglik_categorical_weighted below (logistic only);
+ *   - no weights for OLS (dlsa_ols_fit_batched);
  *   - no int8 exact pass: the exact passes of a weighted fit run on the fp64
  *     MFMA whatever opt->exact_pass says (the digit-grid bound of the int8
  *     pass relies on sqrt(w) <= 1/2, which omega breaks); dlsa_fit_stats
@@ -475,6 +476,43 @@ int dlsa_logistic_fit_categorical(const double* Xn, const uint8_t* codes, const 
                                   const dlsa_fit_options* opt, void* stream);
 
 /*
+ * dlsa_logistic_fit_categorical with per-row prior weights omega, with the
+ * semantics of dlsa_logistic_fit_batched_weighted per partition: the IRLS
+ * weight is omega_i w_i, the score sum_i omega_i (y_i - mu_i) x_i, sig_inv =
+ * X^T diag(omega w) X of the dummy-expanded design at the returned theta,
+ * loglik = sum_i omega_i l_i.  A design made of factors collapses to its
+ * distinct cells: rows (cell, s successes, m trials) with y = s / m and omega
+ * = m give the MLE and sig_inv of the m-times replicated 0/1 rows.
+ *  row_weight  [n_total] fp64, device, finite and >= 0.  NULL: exactly
+ *              dlsa_logistic_fit_categorical, the same kernels and bits.
+ * omega_i = 0 drops row i (its x and y must still be finite).
+ * Statuses, decided before any Newton pass, each with all-zero outputs and
+ * no effect on another partition: (1) a negative or non-finite omega ends the
+ * partition DLSA_STATUS_NONFINITE; (2) sum omega = 0 DLSA_STATUS_SINGULAR;
+ * (3) a partition still running gets DLSA_STATUS_MISSING_LEVEL when some dummy
+ * column has no row with omega > 0 (rows with omega = 0 count as absent).  A
+ * code >= levels[f] fails the call with DLSA_E_INVALID whatever its row's
+ * weight.
+ * Fixed-point bins: every bin term carries omega, so the partition's grids are
+ * those of the unweighted fit divided by omega_max,k, its largest finite
+ * weight (omega == 1: the unweighted grids).  The result stays bit-identical
+ * run to run; a bin's rounding error relative to the column's scale is
+ * ~1e-13 x omega_max / mean omega, and a huge weight coarsens only its own
+ * partition's bins.  The weights are one more 8 B/row stream of every pass
+ * (93 instead of 85 B/row at the airline shape).
+ */
+int dlsa_logistic_fit_categorical_weighted(const double* Xn, const uint8_t* codes,
+                                           const double* y, const double* row_weight,
+                                           const int64_t* offsets, int32_t K, int32_t q,
+                                           int32_t F, const int32_t* levels,
+                                           int32_t fit_intercept, const double* center,
+                                           const double* scale, int32_t max_iter,
+                                           double tol, double* theta, double* sig_inv,
+                                           double* sig_inv_theta, double* loglik,
+                                           int32_t* iters, int32_t* status,
+                                           const dlsa_fit_options* opt, void* stream);
+
+/*
  * dlsa_logistic_loglik_batched with the job-level total of the reference's
  * second pass (the group-by sum of dlsa/model_eval.py:38):
  *   loglik_sum[b] = sum_k loglik[k * n_beta + b], k ascending, from one small
@@ -512,6 +550,25 @@ int dlsa_logistic_loglik_categorical(const double* Xn, const uint8_t* codes, con
                                      const double* betas, int32_t n_beta,
                                      int32_t rows_per_chunk, double* loglik,
                                      double* loglik_sum, void* stream);
+
+/*
+ * dlsa_logistic_loglik_categorical with the prior weights of
+ * dlsa_logistic_fit_categorical_weighted:
+ *   loglik[k * n_beta + b] = sum_i omega_i (y_i eta_i - log(1 + exp(eta_i))).
+ * row_weight [n_total] fp64, device; NULL: exactly the unweighted entry,
+ * bit-identical.  The weights are not checked here: a non-finite omega makes
+ * its own partition's sums non-finite.  8 q + F + 16 bytes per row; same
+ * limits and fixed summation order.
+ */
+int dlsa_logistic_loglik_categorical_weighted(const double* Xn, const uint8_t* codes,
+                                              const double* y, const double* row_weight,
+                                              const int64_t* offsets, int32_t K, int32_t q,
+                                              int32_t F, const int32_t* levels,
+                                              int32_t fit_intercept, const double* center,
+                                              const double* scale, const double* betas,
+                                              int32_t n_beta, int32_t rows_per_chunk,
+                                              double* loglik, double* loglik_sum,
+                                              void* stream);
 
 /* Timing/iteration record of the calling thread's last fit. */
 int dlsa_last_fit_stats(dlsa_fit_stats* out);

@@ -3,12 +3,16 @@
 shape, for A/B runs across library builds (DLSA_LIB) in separate processes.
 
     DLSA_LIB=var/libdlsa_hip_<v>.so python tools/cat_pass_bench.py [--n 120000000] [--K 120]
+                                                                   [--weights real]
 
 Each fit runs max_iter = 1: one full-data Newton pass from theta = 0 plus the
 polish pass at the returned theta, i.e. exactly two full
 passes whatever the kernel's numerics, so ablation builds time the same work.
 Prints one JSON line: the median per-pass time over --rounds fits and the
-algorithmic GB/s (8 q + F + 8 bytes per row).
+algorithmic GB/s (8 q + F + 8 bytes per row).  --weights ones | real times
+the weighted pass (logistic_model_batched_categorical_weighted, 8 more bytes
+per row: omega = 1, or U(0.2, 5) with one row in 50 at 0); the presence pass
+of either fit is read off a kernel trace of this tool (cat_presence_kernel).
 """
 
 import argparse
@@ -26,6 +30,7 @@ def main():
     ap.add_argument("--n", type=int, default=120_000_000)
     ap.add_argument("--K", type=int, default=120)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--weights", choices=["none", "ones", "real"], default="none")
     ap.add_argument("--tag", default=os.environ.get("DLSA_LIB", "in-tree"))
     args = ap.parse_args()
 
@@ -37,17 +42,26 @@ def main():
     Xn, codes, y, levels = M.simulate_categorical(args.n, seed=2019, device="cuda")
     off = (np.arange(args.K + 1, dtype=np.int64) * args.n) // args.K
     row_bytes = 8 * Xn.shape[1] + codes.shape[1] + 8
+    w = None
+    if args.weights != "none":
+        row_bytes += 8
+        w = torch.ones(args.n, dtype=torch.float64, device="cuda")
+        if args.weights == "real":
+            g = torch.Generator(device="cuda").manual_seed(11)
+            w.uniform_(0.2, 5.0, generator=g)
+            w[torch.randint(0, args.n, (args.n // 50,), generator=g, device="cuda")] = 0.0
     per = []
     for r in range(args.rounds + 1):
-        fit = M.logistic_model_batched_categorical(Xn, codes, y, off, levels, fit_intercept=True,
-                                                   max_iter=1, record_timing=True)
+        fit = M.logistic_model_batched_categorical_weighted(
+            Xn, codes, y, off, levels, w, fit_intercept=True, max_iter=1, record_timing=True)
         st = fit.stats
         if r:  # the first fit warms up
             per.append(st["ms_pass_fp64"] / st["passes_fp64"])
         del fit
     torch.cuda.synchronize()
     ms = statistics.median(per)
-    print(json.dumps({"lib": args.tag, "n": args.n, "K": args.K, "passes_per_fit": st["passes_fp64"],
+    print(json.dumps({"lib": args.tag, "n": args.n, "K": args.K, "weights": args.weights,
+                      "passes_per_fit": st["passes_fp64"],
                       "ms_per_pass": ms, "ms_all": per,
                       "GBps": args.n * row_bytes / (ms * 1e-3) / 1e9}), flush=True)
 

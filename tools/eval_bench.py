@@ -5,6 +5,8 @@ dlsa/model_eval.py:10-42) through the C-ABI, three legs:
   dense_p100              dlsa_logistic_loglik_batched_sum at a config-2-like shape (p = 100)
   codes_config3           dlsa_logistic_loglik_categorical at the config-3 shape
                           (AIRLINE_NUMERIC numeric columns + AIRLINE_FACTORS codes)
+  codes_config3_weighted  dlsa_logistic_loglik_categorical_weighted on the same rows with
+                          omega ~ U(0.2, 5) (8 more bytes per row); leg name "weighted"
   dense_expanded_config3  the dense pass on expand_categorical of the same rows: what
                           the evaluation had to read before the code-layout pass
 
@@ -100,6 +102,13 @@ def main():
         legs["codes_config3"], tot_c = timed(lambda out, tot: lib.dlsa_logistic_loglik_categorical(
             M._ptr(Xn), M._ptr(codes), M._ptr(y), off_p, K, q, F, lv_p, 1, None, None,
             M._ptr(betas), B, 0, M._ptr(out), M._ptr(tot), stream), 8 * q + F + 8)
+    if "weighted" in want:
+        w = torch.empty(n, dtype=torch.float64, device=dev).uniform_(0.2, 5.0)
+        legs["codes_config3_weighted"], _ = timed(
+            lambda out, tot: lib.dlsa_logistic_loglik_categorical_weighted(
+                M._ptr(Xn), M._ptr(codes), M._ptr(y), M._ptr(w), off_p, K, q, F, lv_p, 1, None,
+                None, M._ptr(betas), B, 0, M._ptr(out), M._ptr(tot), stream), 8 * q + F + 16)
+        del w
     if "expanded" in want:
         X = M.expand_categorical(Xn, codes, levels)
         del Xn, codes
