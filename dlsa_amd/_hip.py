@@ -139,6 +139,16 @@ SIGNATURES = {
         ctypes.c_int,
         [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _F64, _P, _P, _P, _P, _P,
          _P, ctypes.POINTER(FitOptions), _P]),
+    # the Poisson categorical entries: eta_offset [n] and row_weight [n] (either may be
+    # null) inserted after y
+    "dlsa_poisson_fit_categorical": (
+        ctypes.c_int,
+        [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _F64, _P, _P, _P, _P,
+         _P, _P, ctypes.POINTER(FitOptions), _P]),
+    "dlsa_poisson_loglik_categorical": (
+        ctypes.c_int,
+        [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _P, _P,
+         _P]),
     "dlsa_partition_rows": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "dlsa_last_fit_stats": (ctypes.c_int, [ctypes.POINTER(FitStats)]),
     "dlsa_reduce_partitions": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P]),

@@ -189,8 +189,8 @@ int dlsa_logistic_fit_categorical(const double* Xn, const uint8_t* codes, const 
                                   double tol, double* theta, double* sig_inv,
                                   double* sig_inv_theta, double* loglik, int32_t* iters,
                                   int32_t* status, const dlsa_fit_options* opt, void* stream) {
-  return fit_categorical(Xn, codes, y, nullptr, offsets, K, q, F, levels, fit_intercept, center,
-                         scale, max_iter, tol,
+  return fit_categorical(FAMILY_LOGISTIC, Xn, codes, y, nullptr, nullptr, offsets, K, q, F, levels,
+                         fit_intercept, center, scale, max_iter, tol,
                          {theta, sig_inv, sig_inv_theta, loglik, iters, status}, opt, stream);
 }
 
@@ -202,8 +202,21 @@ int dlsa_logistic_fit_categorical_weighted(const double* Xn, const uint8_t* code
                                            double* theta, double* sig_inv, double* sig_inv_theta,
                                            double* loglik, int32_t* iters, int32_t* status,
                                            const dlsa_fit_options* opt, void* stream) {
-  return fit_categorical(Xn, codes, y, row_weight, offsets, K, q, F, levels, fit_intercept, center,
-                         scale, max_iter, tol,
+  return fit_categorical(FAMILY_LOGISTIC, Xn, codes, y, nullptr, row_weight, offsets, K, q, F,
+                         levels, fit_intercept, center, scale, max_iter, tol,
+                         {theta, sig_inv, sig_inv_theta, loglik, iters, status}, opt, stream);
+}
+
+int dlsa_poisson_fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
+                                 const double* eta_offset, const double* row_weight,
+                                 const int64_t* offsets, int32_t K, int32_t q, int32_t F,
+                                 const int32_t* levels, int32_t fit_intercept,
+                                 const double* center, const double* scale, int32_t max_iter,
+                                 double tol, double* theta, double* sig_inv,
+                                 double* sig_inv_theta, double* loglik, int32_t* iters,
+                                 int32_t* status, const dlsa_fit_options* opt, void* stream) {
+  return fit_categorical(FAMILY_POISSON, Xn, codes, y, eta_offset, row_weight, offsets, K, q, F,
+                         levels, fit_intercept, center, scale, max_iter, tol,
                          {theta, sig_inv, sig_inv_theta, loglik, iters, status}, opt, stream);
 }
 
@@ -371,9 +384,11 @@ int dlsa_poisson_loglik_batched_sum_weighted(const double* X, const double* y,
                       eta_offset, row_weight);
 }
 
-// (row_weight: prior weights or null)
-static int loglik_categorical(const double* Xn, const uint8_t* codes, const double* y,
-                              const double* row_weight, const int64_t* offsets, int32_t K,
+// (eta_offset: FAMILY_POISSON's per-row offset or null; row_weight: prior
+// weights or null)
+static int loglik_categorical(int family, const double* Xn, const uint8_t* codes, const double* y,
+                              const double* eta_offset, const double* row_weight,
+                              const int64_t* offsets, int32_t K,
                               int32_t q, int32_t F, const int32_t* levels, int32_t fit_intercept,
                               const double* center, const double* scale, const double* betas,
                               int32_t n_beta, int32_t rows_per_chunk, double* loglik,
@@ -388,7 +403,9 @@ static int loglik_categorical(const double* Xn, const uint8_t* codes, const doub
   if (rc != DLSA_OK) return rc;
   if (n_beta < 1 || n_beta > kEvalCatMaxB || rows_per_chunk < 0 || !betas || !loglik ||
       (center == nullptr) != (scale == nullptr)) {
-    set_error("dlsa_logistic_loglik_categorical: invalid arguments (1 <= n_beta <= 16, "
+    set_error(std::string(family == FAMILY_POISSON ? "dlsa_poisson_loglik_categorical"
+                                                   : "dlsa_logistic_loglik_categorical") +
+              ": invalid arguments (1 <= n_beta <= 16, "
               "rows_per_chunk >= 0, center and scale both or neither)");
     return DLSA_E_INVALID;
   }
@@ -397,7 +414,12 @@ static int loglik_categorical(const double* Xn, const uint8_t* codes, const doub
     set_error("null Xn, codes or y");
     return DLSA_E_INVALID;
   }
-  EvalCatArgsWgt ea;  // (the unweighted kernels take its EvalCatArgs slice)
+  const bool pois = family == FAMILY_POISSON;
+  if (eta_offset && !pois) {
+    set_error("eta_offset is the Poisson family's");
+    return DLSA_E_INVALID;
+  }
+  EvalCatArgsPois ea;  // (every kernel takes its slice: EvalCatArgs, EvalCatArgsWgt or all)
   memset(&ea, 0, sizeof(ea));
   ea.q = q;
   ea.F = F;
@@ -409,7 +431,7 @@ static int loglik_categorical(const double* Xn, const uint8_t* codes, const doub
     ea.toff[f] = o;
     o += levels[f];
   }
-  if (!eval_cat_plan(ea, row_weight != nullptr)) {
+  if (!eval_cat_plan(ea, (eta_offset ? EX_OFS : 0) | (row_weight ? EX_WGT : 0))) {
     set_error("categorical evaluation: the coefficient table does not fit the LDS");
     return DLSA_E_UNSUPPORTED;
   }
@@ -451,7 +473,10 @@ static int loglik_categorical(const double* Xn, const uint8_t* codes, const doub
     ea.y_last4 = (uintptr_t)(y + n_total) - 4;
     ea.row_weight = row_weight;
     if (row_weight) ea.w_last4 = (uintptr_t)(row_weight + n_total) - 4;
-    DLSA_HIP_TRY(launch_loglik_cat(ea, pl.n_chunks, stream));
+    ea.eta_offset = eta_offset;
+    if (eta_offset) ea.o_last4 = (uintptr_t)(eta_offset + n_total) - 4;
+    DLSA_HIP_TRY(pois ? launch_loglik_cat_pois(ea, pl.n_chunks, stream)
+                      : launch_loglik_cat(ea, pl.n_chunks, stream));
     DLSA_HIP_TRY(hipMemcpyAsync(h_bad.data(), d_bad, 4LL * pl.n_chunks, hipMemcpyDeviceToHost,
                                 stream));
   }
@@ -476,7 +501,8 @@ int dlsa_logistic_loglik_categorical(const double* Xn, const uint8_t* codes, con
                                      const double* center, const double* scale,
                                      const double* betas, int32_t n_beta, int32_t rows_per_chunk,
                                      double* loglik, double* loglik_sum, void* stream) {
-  return loglik_categorical(Xn, codes, y, nullptr, offsets, K, q, F, levels, fit_intercept,
+  return loglik_categorical(FAMILY_LOGISTIC, Xn, codes, y, nullptr, nullptr, offsets, K, q, F,
+                            levels, fit_intercept,
                             center, scale, betas, n_beta, rows_per_chunk, loglik, loglik_sum,
                             stream);
 }
@@ -489,9 +515,21 @@ int dlsa_logistic_loglik_categorical_weighted(const double* Xn, const uint8_t* c
                                               const double* scale, const double* betas,
                                               int32_t n_beta, int32_t rows_per_chunk,
                                               double* loglik, double* loglik_sum, void* stream) {
-  return loglik_categorical(Xn, codes, y, row_weight, offsets, K, q, F, levels, fit_intercept,
-                            center, scale, betas, n_beta, rows_per_chunk, loglik, loglik_sum,
-                            stream);
+  return loglik_categorical(FAMILY_LOGISTIC, Xn, codes, y, nullptr, row_weight, offsets, K, q, F,
+                            levels, fit_intercept, center, scale, betas, n_beta, rows_per_chunk,
+                            loglik, loglik_sum, stream);
+}
+
+int dlsa_poisson_loglik_categorical(const double* Xn, const uint8_t* codes, const double* y,
+                                    const double* eta_offset, const double* row_weight,
+                                    const int64_t* offsets, int32_t K, int32_t q, int32_t F,
+                                    const int32_t* levels, int32_t fit_intercept,
+                                    const double* center, const double* scale,
+                                    const double* betas, int32_t n_beta, int32_t rows_per_chunk,
+                                    double* loglik, double* loglik_sum, void* stream) {
+  return loglik_categorical(FAMILY_POISSON, Xn, codes, y, eta_offset, row_weight, offsets, K, q,
+                            F, levels, fit_intercept, center, scale, betas, n_beta,
+                            rows_per_chunk, loglik, loglik_sum, stream);
 }
 
 int dlsa_partition_rows(const int32_t* part_id, int64_t n, int32_t K, int32_t n_arrays,

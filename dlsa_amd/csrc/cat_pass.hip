@@ -50,7 +50,7 @@ size_t cat_lds_bytes(const CatArgs& a) {
 }
 
 hipError_t launch_cat_pass(const CatArgs& a, bool standardize, int n_chunks, hipStream_t s) {
-  return launch_cat_pass_t<false>(a, standardize, n_chunks, s);
+  return launch_cat_pass_t<FAMILY_LOGISTIC, EX_NONE>(a, standardize, n_chunks, s);
 }
 
 hipError_t launch_cat_presence(const CatArgs& a, int n_chunks, int32_t* counts, int32_t* bad,

@@ -42,7 +42,9 @@
 //
 // This header holds the kernel templates and their launchers.  cat_pass.hip
 // instantiates the unweighted kernels (CatArgs), cat_pass_wgt.hip the ones
-// with per-row prior weights (WGT: CatArgsWgt, omega = a.row_weight[row]).
+// with per-row prior weights (WGT: CatArgsWgt, omega = a.row_weight[row]),
+// cat_pass_pois*.hip the Poisson family's, one unit per row-extras mask
+// (CatArgsPois, cat_pois_impl.hpp).
 #pragma once
 #include <math.h>
 
@@ -102,9 +104,21 @@ __host__ __device__ __forceinline__ int cat_pair(int f, int g, int F) {
 // the fold factor's intercept row and the pair cells are formed from those
 // two products as before.  The grids carry the partition's omega_max
 // (fit_cat.hip cat_grids), so every term stays below 2^50.
-template <int QN, int FM, int NTHR, bool STD, bool EX, bool WGT>
+// FAM, RX: the family and the row-extras mask (EX_WGT is WGT above).  The
+// Poisson arm is mu = exp(e), w = mu, res = y - mu, with the per-row offset
+// (EX_OFS) added to e; slab_ll takes the constant-free sum omega (y eta - mu),
+// slab_llc the sum of -omega lgamma(y + 1), and the workgroup folds the
+// largest omega mu of its rows into mumax[part] (the next pass's grids, DESIGN
+// 4.5h).  Its grids are written before the pass by launch_cat_pois_grid; a
+// NaN hscale[0] marks a partition no grid can serve: the workgroup skips its
+// rows and publishes a NaN log-likelihood, which the solve takes as an
+// overshoot.
+template <int QN, int FM, int NTHR, bool STD, bool EX, int FAM, int RX>
 __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
-    const typename cat_args_of<WGT>::type a) {
+    const typename cat_pass_args_of<FAM, RX>::type a) {
+  constexpr bool WGT = (RX & EX_WGT) != 0, OFS = (RX & EX_OFS) != 0;
+  constexpr bool POIS = FAM == FAMILY_POISSON;
+  static_assert(POIS || !OFS, "the offset is the Poisson family's");
   extern __shared__ __attribute__((aligned(16))) double sm[];
   constexpr int NW = NTHR / 64;
   // EX: the intercept row of the dense block (sum w, sum w x_i) and the
@@ -162,7 +176,9 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
   __syncthreads();
 
   const int64_t row0 = a.chunk_row0[chunk];
-  const int nrows = a.chunk_rows[chunk];
+  // (POIS: no rows for a partition whose grids could not be made)
+  const bool no_grid = POIS && isnan(a.hscale[(int64_t)part * (kCatQMax + 2)]);
+  const int nrows = no_grid ? 0 : a.chunk_rows[chunk];
   // fixed-point scales in registers (not re-read from the kernel arguments
   // inside the row loop): [0] w, [1] residual, [2 + i - ic] w x_i
   double hsc[QN + 2];
@@ -188,6 +204,9 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
   int cl[FM];
   double yl;
   [[maybe_unused]] double oml = 1.0;  // WGT: the row's prior weight
+  [[maybe_unused]] double ofl = 0.0;  // OFS: the row's offset
+  [[maybe_unused]] double llcacc = 0.0;            // POIS: sum of -omega lgamma(y + 1)
+  [[maybe_unused]] unsigned long long mubits = 0;  // POIS: max mu as bits
   auto load_row = [&](int rr) {
     const int64_t rw = row0 + rr;
     const int64_t rl = (DLSA_CAT_ABLATE & 32) ? row0 + (rr & 1023) % nrows : rw;
@@ -211,6 +230,7 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
     }
     yl = a.y[rl];
     if constexpr (WGT) oml = a.row_weight[rl];
+    if constexpr (OFS) ofl = a.eta_offset[rl];
   };
   if (tid < nrows) load_row(tid);
   for (int r = tid; r < nrows; r += NTHR) {
@@ -261,17 +281,39 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
     }
 #pragma unroll
     for (int f = 0; f < FM; ++f) e0 += de[f];
-    const double e = e0 + e1;
-    const LogisticLink k = logistic_link<RCP_DIV>(e);
-    double w = k.w;
-    double res = yv - k.mu;
-    if constexpr (WGT) {
-      const double om = oml;
-      w *= om;
-      res *= om;
-      llacc += om * (yv * e - (fmax(e, 0.0) + log1p(k.ea)));
+    double w, res;
+    if constexpr (POIS) {
+      double e = e0 + e1;
+      if constexpr (OFS) e += ofl;
+      const double mu = exp(e);
+      w = mu;
+      res = yv - mu;
+      if constexpr (WGT) {
+        const double om = oml;
+        w *= om;
+        res *= om;
+        llacc += om * (yv * e - mu);
+        llcacc -= om * lgamma1p(yv);
+      } else {
+        llacc += yv * e - mu;
+        llcacc -= lgamma1p(yv);
+      }
+      // the measured maximum is of omega mu, the term the bins take: a heavy
+      // weight and a large mu on different rows do not multiply in the bound
+      mubits = max(mubits, (unsigned long long)__double_as_longlong(w));
     } else {
-      llacc += yv * e - (fmax(e, 0.0) + log1p(k.ea));
+      const double e = e0 + e1;
+      const LogisticLink k = logistic_link<RCP_DIV>(e);
+      w = k.w;
+      res = yv - k.mu;
+      if constexpr (WGT) {
+        const double om = oml;
+        w *= om;
+        res *= om;
+        llacc += om * (yv * e - (fmax(e, 0.0) + log1p(k.ea)));
+      } else {
+        llacc += yv * e - (fmax(e, 0.0) + log1p(k.ea));
+      }
     }
 
 #pragma unroll
@@ -369,6 +411,19 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
   // round trips; 0.015 ms per launch, profiles/r05cf_cat_epilogue_ab.jsonl)
   double* hsl = th;
   for (int i = tid; i < kCatQMax + 2; i += NTHR) hsl[i] = hs[i];
+  // POIS: the waves' constant-term sums and largest mu, behind the grids
+  constexpr int kLlcAt = 32, kMuAt = 48;
+  static_assert(kCatQMax + 2 <= kLlcAt && kLlcAt + NW <= kMuAt && kMuAt + NW <= kCatPMax);
+  if constexpr (POIS) {
+    const double v = wave_red(llcacc);
+    unsigned long long m = mubits;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) m = max(m, (unsigned long long)__shfl_xor((long long)m, o));
+    if (lane == 0) {
+      hsl[kLlcAt + wid] = v;
+      ((unsigned long long*)hsl)[kMuAt + wid] = m;
+    }
+  }
   __syncthreads();
 
   // factor of dummy parameter index d (0-based among dummies)
@@ -456,7 +511,23 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
     }
     a.slab_g[(int64_t)chunk * PP + e] = v;
   }
-  if (tid == 0) a.slab_ll[chunk] = fin[NTRI + NQ];
+  if constexpr (POIS) {
+    if (tid == 0) {
+      double c = 0.0;
+      unsigned long long m = 0ull;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        c += hsl[kLlcAt + w];
+        m = max(m, ((const unsigned long long*)hsl)[kMuAt + w]);
+      }
+      a.slab_ll[chunk] = isnan(hsl[0]) ? hsl[0] : fin[NTRI + NQ];
+      a.slab_llc[chunk] = c;
+      if (m)
+        __hip_atomic_fetch_max(&a.mumax[part], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  } else {
+    if (tid == 0) a.slab_ll[chunk] = fin[NTRI + NQ];
+  }
 }
 
 // Level presence per chunk: counts[chunk, d] = 1 if a row of the chunk
@@ -655,13 +726,13 @@ constexpr int cat_threads_t(int QN, int FM) {
   return (QN <= 4 || (QN <= 10 && FM <= 8)) ? 512 : 256;
 }
 
-template <int QN, int FM, int NTHR, bool STD, bool WGT>
-static hipError_t launch_cat_t(const typename cat_args_of<WGT>::type& a, int n_chunks, size_t lds,
-                               hipStream_t s) {
+template <int QN, int FM, int NTHR, bool STD, int FAM, int RX>
+static hipError_t launch_cat_t(const typename cat_pass_args_of<FAM, RX>::type& a, int n_chunks,
+                               size_t lds, hipStream_t s) {
   // the exact-bucket kernel only where it exists (F <= 8) and folds (F >= 1)
   const bool ex = FM == 8 && cat_exact_bucket(a) && a.fold >= 0;
-  auto kern = ex ? cat_pass_kernel<QN, FM, NTHR, STD, FM == 8, WGT>
-                 : cat_pass_kernel<QN, FM, NTHR, STD, false, WGT>;
+  auto kern = ex ? cat_pass_kernel<QN, FM, NTHR, STD, FM == 8, FAM, RX>
+                 : cat_pass_kernel<QN, FM, NTHR, STD, false, FAM, RX>;
   {
     hipError_t e = ensure_max_lds((const void*)kern, 160 * 1024 - kCatStaticLds);
     if (e != hipSuccess) return e;
@@ -670,35 +741,35 @@ static hipError_t launch_cat_t(const typename cat_args_of<WGT>::type& a, int n_c
   return hipGetLastError();
 }
 
-template <int QN, bool WGT>
-static hipError_t launch_cat_q(const typename cat_args_of<WGT>::type& a, bool std_, int n_chunks,
-                               size_t lds, hipStream_t s) {
+template <int QN, int FAM, int RX>
+static hipError_t launch_cat_q(const typename cat_pass_args_of<FAM, RX>::type& a, bool std_,
+                               int n_chunks, size_t lds, hipStream_t s) {
   // 512 threads while the register blocks fit 256 VGPRs (measured: QN <= 10
   // with F <= 8), else 256 threads (512 VGPRs per lane)
   if (a.F <= 8) {
     constexpr int N8 = cat_threads_t(QN, 8);
-    return std_ ? launch_cat_t<QN, 8, N8, true, WGT>(a, n_chunks, lds, s)
-                : launch_cat_t<QN, 8, N8, false, WGT>(a, n_chunks, lds, s);
+    return std_ ? launch_cat_t<QN, 8, N8, true, FAM, RX>(a, n_chunks, lds, s)
+                : launch_cat_t<QN, 8, N8, false, FAM, RX>(a, n_chunks, lds, s);
   }
   constexpr int N16 = cat_threads_t(QN, 16);
-  return std_ ? launch_cat_t<QN, 16, N16, true, WGT>(a, n_chunks, lds, s)
-              : launch_cat_t<QN, 16, N16, false, WGT>(a, n_chunks, lds, s);
+  return std_ ? launch_cat_t<QN, 16, N16, true, FAM, RX>(a, n_chunks, lds, s)
+              : launch_cat_t<QN, 16, N16, false, FAM, RX>(a, n_chunks, lds, s);
 }
 
-// the body of launch_cat_pass / launch_cat_pass_wgt
-template <bool WGT>
-static hipError_t launch_cat_pass_t(const typename cat_args_of<WGT>::type& a, bool standardize,
-                                    int n_chunks, hipStream_t s) {
+// the body of launch_cat_pass / launch_cat_pass_wgt / launch_cat_pass_pois_unit
+template <int FAM, int RX>
+static hipError_t launch_cat_pass_t(const typename cat_pass_args_of<FAM, RX>::type& a,
+                                    bool standardize, int n_chunks, hipStream_t s) {
   if (n_chunks <= 0) return hipSuccess;
   const size_t lds = cat_lds_bytes(a);
   if (lds + kCatStaticLds > 160 * 1024 || a.F > kCatMaxFactors || a.q + a.intercept > kCatQMax)
     return hipErrorInvalidValue;
   switch (cat_qn(a.intercept + a.q)) {
-    case 4: return launch_cat_q<4, WGT>(a, standardize, n_chunks, lds, s);
-    case 8: return launch_cat_q<8, WGT>(a, standardize, n_chunks, lds, s);
-    case 10: return launch_cat_q<10, WGT>(a, standardize, n_chunks, lds, s);
-    case 12: return launch_cat_q<12, WGT>(a, standardize, n_chunks, lds, s);
-    default: return launch_cat_q<16, WGT>(a, standardize, n_chunks, lds, s);
+    case 4: return launch_cat_q<4, FAM, RX>(a, standardize, n_chunks, lds, s);
+    case 8: return launch_cat_q<8, FAM, RX>(a, standardize, n_chunks, lds, s);
+    case 10: return launch_cat_q<10, FAM, RX>(a, standardize, n_chunks, lds, s);
+    case 12: return launch_cat_q<12, FAM, RX>(a, standardize, n_chunks, lds, s);
+    default: return launch_cat_q<16, FAM, RX>(a, standardize, n_chunks, lds, s);
   }
 }
 

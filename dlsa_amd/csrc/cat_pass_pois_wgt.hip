@@ -1,0 +1,10 @@
+// Poisson regression on the categorical-code layout with per-row prior weights:
+// the pass and presence kernels of this row-extras mask (cat_pois_impl.hpp;
+// the routing and the grid kernels are cat_pass_pois.hip's).
+#include "cat_pois_impl.hpp"
+
+namespace dlsa {
+
+DLSA_CAT_POIS_UNIT(EX_WGT)
+
+}  // namespace dlsa

@@ -9,7 +9,7 @@ namespace dlsa {
 hipError_t launch_cat_pass_wgt(const CatArgsWgt& a, bool standardize, int n_chunks,
                                hipStream_t s) {
   if (!a.row_weight) return hipErrorInvalidValue;
-  return launch_cat_pass_t<true>(a, standardize, n_chunks, s);
+  return launch_cat_pass_t<FAMILY_LOGISTIC, EX_WGT>(a, standardize, n_chunks, s);
 }
 
 hipError_t launch_cat_presence_wgt(const CatArgsWgt& a, int n_chunks, int32_t* counts,

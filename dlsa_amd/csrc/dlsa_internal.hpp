@@ -520,6 +520,24 @@ template <bool WGT>
 struct cat_args_of {
   typedef typename std::conditional<WGT, CatArgsWgt, CatArgs>::type type;
 };
+// CatArgs of the Poisson instantiations (cat_pass_pois*.hip), every row-extras
+// mask alike: mu = exp(eta + eta_offset) is unbounded, so each pass also
+// measures its largest mu per partition, from which the grids of the next pass
+// are sized on the device (launch_cat_pois_grid).  CatArgs and CatArgsWgt keep
+// their sizes.
+struct CatArgsPois : CatArgsWgt {
+  const double* eta_offset;   // [n_total] or null (the kernels without EX_OFS)
+  double* slab_llc;           // [n_chunks] partial sums of -omega lgamma(y + 1)
+  unsigned long long* mumax;  // [K] the pass's largest omega mu as bits (>= 0: ordered like its bits)
+  double* ymax;               // [n_chunks] the presence pass's largest finite y
+  double* omax;               // [n_chunks] ... and largest finite eta_offset (> 0, else 0)
+};
+// the kernel argument of a family's pass with row-extras mask RX
+template <int FAM, int RX>
+struct cat_pass_args_of {
+  typedef typename std::conditional<FAM == FAMILY_POISSON, CatArgsPois,
+                                    typename cat_args_of<(RX & EX_WGT) != 0>::type>::type type;
+};
 
 // Log-likelihood evaluation pass on the categorical-code layout
 // (eval_cat_pass.hip): P <= DLSA_MAX_P, the other limits are the fit's.
@@ -549,10 +567,19 @@ struct EvalCatArgsWgt : EvalCatArgs {
   const double* row_weight;  // [n_total] or null (the unweighted kernels, which take EvalCatArgs)
   uintptr_t w_last4;         // last 4-B address inside row_weight
 };
-// sets rb and nslot (weighted: the ring slot also holds omega); false: does not fit the LDS
-bool eval_cat_plan(EvalCatArgs& a, bool weighted = false);
+// ... of the Poisson kernels (eval_cat_pass_pois.hip), every mask alike: the
+// per-row offset is one more 256-byte-piece stream, behind y and before omega
+struct EvalCatArgsPois : EvalCatArgsWgt {
+  const double* eta_offset;  // [n_total] or null
+  uintptr_t o_last4;         // last 4-B address inside eta_offset
+};
+// sets rb and nslot (extras: the EX_* mask of the row extras the ring slot
+// also holds); false: does not fit the LDS
+bool eval_cat_plan(EvalCatArgs& a, int extras = EX_NONE);
 // routes on a.row_weight; the unweighted kernels are handed the EvalCatArgs slice
 hipError_t launch_loglik_cat(const EvalCatArgsWgt& a, int n_chunks, hipStream_t s);
+// FAMILY_POISSON: routes on a.eta_offset and a.row_weight
+hipError_t launch_loglik_cat_pois(const EvalCatArgsPois& a, int n_chunks, hipStream_t s);
 hipError_t launch_loglik_total(const double* ll, int K, int B, double* out, hipStream_t s);
 
 // Row repartitioning (partition_rows.hip): stable counting sort by partition id.
@@ -587,6 +614,37 @@ hipError_t launch_cat_pass_wgt(const CatArgsWgt& a, bool standardize, int n_chun
                                hipStream_t s);
 hipError_t launch_cat_presence_wgt(const CatArgsWgt& a, int n_chunks, int32_t* counts,
                                    int32_t* bad, double* colmax, hipStream_t s);
+// FAMILY_POISSON on the code layout (cat_pass_pois*.hip): one unit per
+// row-extras mask RX holds its pass kernels and its presence kernel (row
+// oriented like the weighted one; it also clears and fills a.ymax and, by RX,
+// a.omax and a.wmax); the two launchers below route on a.eta_offset and
+// a.row_weight.
+template <int RX>
+hipError_t launch_cat_pass_pois_unit(const CatArgsPois& a, bool standardize, int n_chunks,
+                                     hipStream_t s);
+template <int RX>
+hipError_t launch_cat_presence_pois_unit(const CatArgsPois& a, int n_chunks, int32_t* counts,
+                                         int32_t* bad, double* colmax, hipStream_t s);
+hipError_t launch_cat_pass_pois(const CatArgsPois& a, bool standardize, int n_chunks,
+                                hipStream_t s);
+hipError_t launch_cat_presence_pois(const CatArgsPois& a, int n_chunks, int32_t* counts,
+                                    int32_t* bad, double* colmax, hipStream_t s);
+// The per-partition bounds the Poisson grids are sized from, fixed after the
+// presence pass: bounds [K][kCatPoisBounds] = m~_j (the bound on the
+// standardised column j) for j < kCatQMax, then o_max, omega_max, y_max.  Also
+// puts theta[k][0] of a MISSING_LEVEL partition back to 0 (the pre-pass wrote
+// the start point there before the mark kernel ended the partition).
+constexpr int kCatPoisBounds = kCatQMax + 3;
+hipError_t launch_cat_pois_bounds(const CatArgsPois& a, const int32_t* pcb, int K,
+                                  const double* colmax, double* bounds, double* theta,
+                                  const int32_t* status, hipStream_t s);
+// Before every Poisson pass: the hscale row of each running partition from an
+// upper bound on its rows' eta at the pass's theta, theta
+// snapshotted into theta_snap [K, P] and a.mumax cleared for the pass.  rmax:
+// the most rows of a chunk, at least 1024.  A partition no grid can serve
+// gets hscale[0] = NaN: its pass publishes a non-finite log-likelihood.
+hipError_t launch_cat_pois_grid(const CatArgsPois& a, int K, const double* bounds,
+                                double* theta_snap, double* hscale, double rmax, hipStream_t s);
 hipError_t launch_wide_row(const WideArgs& a, bool standardize, int family, int n_chunks,
                            hipStream_t s);
 hipError_t launch_wide_gram(const WideArgs& a, bool standardize, hipStream_t s);

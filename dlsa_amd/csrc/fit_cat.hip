@@ -6,6 +6,10 @@
 // weighted fits decides NONFINITE / SINGULAR first, the presence pass counts a
 // level only in rows with omega > 0 and takes the partition's omega_max, which
 // scales the grids, and the passes are cat_pass_wgt.hip's.
+// FAMILY_POISSON (cat_pass_pois*.hip), with an optional per-row offset and
+// optional prior weights: the dense Poisson fit's start point, pre-pass
+// statuses and constant term (fit_fused.hip), a single plan level, and grids
+// written on the device before every pass instead of cat_grids' (DESIGN 4.5h).
 #include "fit_driver.hpp"
 
 namespace dlsa {
@@ -62,8 +66,9 @@ std::vector<double> cat_grids(const std::vector<Plan>& plans, int K, int q, bool
 
 }  // namespace
 
-int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
-                    const double* row_weight, const int64_t* offsets, int32_t K, int32_t q,
+int fit_categorical(int family, const double* Xn, const uint8_t* codes, const double* y,
+                    const double* eta_offset, const double* row_weight, const int64_t* offsets,
+                    int32_t K, int32_t q,
                     int32_t F, const int32_t* levels, int32_t fit_intercept, const double* center,
                     const double* scale, int32_t max_iter, double tol, const FitOutputs& out,
                     const dlsa_fit_options* opt_in, void* stream_) {
@@ -83,7 +88,16 @@ int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
     return DLSA_E_INVALID;
   }
 
-  CatArgsWgt ca;  // (the unweighted kernels take its CatArgs slice)
+  const bool pois = family == FAMILY_POISSON;
+  if (family != FAMILY_LOGISTIC && !pois) {
+    set_error("the categorical fit runs the logistic and Poisson families");
+    return DLSA_E_INVALID;
+  }
+  if (eta_offset && !family_rules(family).offset) {
+    set_error("eta_offset is the Poisson family's");
+    return DLSA_E_INVALID;
+  }
+  CatArgsPois ca;  // (every kernel takes its slice: CatArgs, CatArgsWgt or all of it)
   memset(&ca, 0, sizeof(ca));
   ca.q = q;
   ca.F = F;
@@ -122,6 +136,10 @@ int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
   // profiles/r04n_cat_warm_start_ab.txt).  DLSA_WARM_START overrides.
   opt.warm_start = opt.warm_start && K > 0 && n_total / K >= (int64_t(1) << 19);
   if (const char* e = env_knob("DLSA_WARM_START")) opt.warm_start = atoi(e);
+  // Poisson: no warm-start level.  A prefix pass measures mu_max on a prefix
+  // only, so the first full pass after it would take the analytic bound's
+  // coarse grid and could be the published one
+  if (pois) opt.warm_start = 0;
   const std::vector<Plan> plans = level_plans(offsets, K, P - ic, ic, opt.warm_start != 0, cat_rpc);
   const Plan& pl = plans.back();
   const int64_t nc = std::max(pl.n_chunks, 1);
@@ -164,26 +182,56 @@ int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
   }
   DLSA_HIP_TRY(staged_upload(d_offsets, offsets, 8LL * (K + 1), stream));
 
-  SolveArgs sa = newton_solve_args(ws, L.ns, out, P, FAMILY_LOGISTIC, tol);
+  SolveArgs sa = newton_solve_args(ws, L.ns, out, P, family, tol);
   sa.part_chunk_begin = d_pcb;
   sa.slab_H = (double*)ws.at(L.off_slabH);
   sa.slab_g = (double*)ws.at(L.off_slabg);
   sa.slab_ll = (double*)ws.at(L.off_slabll);
   sa.NT = pl.NT;
   sa.escalate_to = PHASE_F64;  // every categorical pass is exact
+  // Poisson: the start values, the constant-term partials and the state of
+  // the grids live in an allocation of the fit's own, as in fit_fused.hip (the
+  // workspace layout is the logistic one)
+  Workspace pws(stream);
+  double *d_bounds = nullptr, *d_thsnap = nullptr;
+  if (pois) {
+    Bump pb;
+    const int64_t off_t0 = pb.take(8LL * std::max(K, 1));
+    const int64_t off_llc = pb.take(8 * nc);
+    const int64_t off_mumax = pb.take(8LL * std::max(K, 1));
+    const int64_t off_snap = pb.take(8LL * std::max(K, 1) * P);
+    const int64_t off_bounds = pb.take(8LL * std::max(K, 1) * kCatPoisBounds);
+    const int64_t off_ymax = pb.take(8 * nc), off_omax = pb.take(8 * nc);
+    const int64_t off_pwmax = pb.take(8 * nc);
+    if (int prc = pws.alloc(pb.o)) return prc;
+    DLSA_HIP_TRY(hipMemsetAsync(pws.at(0), 0, pb.o, stream));
+    sa.theta0 = (const double*)pws.at(off_t0);
+    sa.slab_llc = (double*)pws.at(off_llc);
+    ca.slab_llc = sa.slab_llc;
+    ca.mumax = (unsigned long long*)pws.at(off_mumax);
+    ca.ymax = (double*)pws.at(off_ymax);
+    ca.omax = (double*)pws.at(off_omax);
+    ca.wmax = (double*)pws.at(off_pwmax);
+    d_thsnap = (double*)pws.at(off_snap);
+    d_bounds = (double*)pws.at(off_bounds);
+  }
   DLSA_HIP_TRY(fit_init(sa, d_offsets, K, PHASE_F64, stream));
   // prior weights: a negative or non-finite omega ends its partition
   // NONFINITE, sum omega = 0 SINGULAR, before the presence pass marks missing
   // levels among the partitions still running
-  if (row_weight)
-    DLSA_HIP_TRY(launch_fit_prepass(FAMILY_LOGISTIC, y, nullptr, row_weight, d_offsets, K, P, ic,
-                                    out.theta, nullptr, sa.phase, out.status, stream));
+  // (Poisson: also a negative or non-finite y or offset, sum omega y = 0
+  // SINGULAR, and the start point log(sum omega y / sum omega e^o))
+  if (row_weight || pois)
+    DLSA_HIP_TRY(launch_fit_prepass(family, y, eta_offset, row_weight, d_offsets, K, P, ic,
+                                    out.theta, const_cast<double*>(sa.theta0), sa.phase,
+                                    out.status, stream));
 
   ca.Xn = Xn;
   ca.codes = codes;
   ca.y = y;
   ca.row_weight = row_weight;
-  ca.wmax = row_weight ? (double*)ws.at(off_wmax) : nullptr;
+  ca.eta_offset = eta_offset;
+  if (!pois) ca.wmax = row_weight ? (double*)ws.at(off_wmax) : nullptr;
   ca.chunk_row0 = (const int64_t*)ws.at(L.off_row0);
   ca.chunk_rows = (const int32_t*)ws.at(L.off_rows);
   ca.chunk_part = (const int32_t*)ws.at(L.off_part);
@@ -206,7 +254,9 @@ int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
   std::vector<double> h_colmax((size_t)kCatQMax * nc, 0.0);
   std::vector<double> h_wmax(row_weight ? (size_t)nc : 0, 0.0);
   DLSA_HIP_TRY(upload(pl));
-  if (row_weight) {
+  if (pois) {
+    DLSA_HIP_TRY(launch_cat_presence_pois(ca, pl.n_chunks, d_counts, d_bad, d_colmax, stream));
+  } else if (row_weight) {
     DLSA_HIP_TRY(launch_cat_presence_wgt(ca, pl.n_chunks, d_counts, d_bad, d_colmax, stream));
     if (pl.n_chunks > 0)
       DLSA_HIP_TRY(hipMemcpyAsync(h_wmax.data(), ca.wmax, 8LL * pl.n_chunks,
@@ -228,10 +278,17 @@ int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
     DLSA_HIP_TRY(hipMemcpy(hc.data(), center, 8LL * q, hipMemcpyDeviceToHost));
     DLSA_HIP_TRY(hipMemcpy(hs.data(), scale, 8LL * q, hipMemcpyDeviceToHost));
   }
-  // (staged into the pinned arena on upload)
-  const std::vector<double> h_hs =
-      cat_grids(plans, K, q, center != nullptr, h_colmax, h_wmax, hc, hs);
-  DLSA_HIP_TRY(staged_upload(d_hs, h_hs.data(), 8LL * (kCatQMax + 2) * K, stream));
+  if (pois) {
+    // the grids are written before every pass; here only what they are sized
+    // from, per partition, on the device
+    DLSA_HIP_TRY(launch_cat_pois_bounds(ca, d_pcb, K, d_colmax, d_bounds, out.theta,
+                                        out.status, stream));
+  } else {
+    // (staged into the pinned arena on upload)
+    const std::vector<double> h_hs =
+        cat_grids(plans, K, q, center != nullptr, h_colmax, h_wmax, hc, hs);
+    DLSA_HIP_TRY(staged_upload(d_hs, h_hs.data(), 8LL * (kCatQMax + 2) * K, stream));
+  }
   ca.hscale = d_hs;
   for (int k = 0; k < K; ++k)
     if (h_badp[k]) {
@@ -245,11 +302,17 @@ int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
   const bool standardize = center != nullptr;
   StreamTimer timed{stream, opt.record_timing != 0};
   const bool trace = trace_enabled();
+  const double rmax = (double)std::max(1024, pl.max_chunk_rows);
   auto pass_and_solve = [&](const Plan& qn, const std::vector<int64_t>& part_rows,
                             bool clear_counters) -> hipError_t {
+    if (pois) {  // this pass's grids, from theta and the last pass's largest mu
+      hipError_t eg = launch_cat_pois_grid(ca, K, d_bounds, d_thsnap, d_hs, rmax, stream);
+      if (eg != hipSuccess) return eg;
+    }
     hipError_t e = timed(&g_stats.ms_pass_fp64, [&] {
-      return row_weight ? launch_cat_pass_wgt(ca, standardize, qn.n_chunks, stream)
-                        : launch_cat_pass(ca, standardize, qn.n_chunks, stream);
+      return pois         ? launch_cat_pass_pois(ca, standardize, qn.n_chunks, stream)
+             : row_weight ? launch_cat_pass_wgt(ca, standardize, qn.n_chunks, stream)
+                          : launch_cat_pass(ca, standardize, qn.n_chunks, stream);
     });
     g_stats.passes_fp64++;
     g_stats.rows_fp64 += phase_rows(part_rows, h.phase, PHASE_F64);

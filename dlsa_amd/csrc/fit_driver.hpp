@@ -292,9 +292,11 @@ struct DenseFit {
 };
 int fit_fused(const DenseFit& f);  // P <= DLSA_MAX_P_FUSED (fit_fused.hip)
 int fit_wide(const DenseFit& f);   // P > DLSA_MAX_P_FUSED (fit_wide.hip)
-// (row_weight: prior weights or null)
-int fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
-                    const double* row_weight, const int64_t* offsets, int32_t K, int32_t q, int32_t F,
+// (family: FAMILY_LOGISTIC or FAMILY_POISSON; eta_offset: Poisson's per-row
+// offset or null; row_weight: prior weights or null)
+int fit_categorical(int family, const double* Xn, const uint8_t* codes, const double* y,
+                    const double* eta_offset, const double* row_weight, const int64_t* offsets,
+                    int32_t K, int32_t q, int32_t F,
                     const int32_t* levels, int32_t fit_intercept, const double* center,
                     const double* scale, int32_t max_iter, double tol, const FitOutputs& out,
                     const dlsa_fit_options* opt_in, void* stream);  // fit_cat.hip

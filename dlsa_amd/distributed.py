@@ -89,7 +89,8 @@ def reduce_loglik(ll_kb, group=None):
 
 
 def loglik_sharded(X, y, offsets, betas, fit_intercept=False, center=None, scale=None,
-                   codes=None, levels=None, group=None, sample_weight=None):
+                   codes=None, levels=None, group=None, family="logistic", eta_offset=None,
+                   exposure=None, sample_weight=None):
     """Second pass of a sharded job (dlsa/model_eval.py:10-42): the
     log-likelihood of each candidate row of ``betas`` [B, P] over the whole
     data set.  X, y, offsets describe the LOCAL shard as in
@@ -98,10 +99,25 @@ def loglik_sharded(X, y, offsets, betas, fit_intercept=False, center=None, scale
     this rank's partitions on the device; ONE all-reduce of those B doubles
     gives every rank the global sums.  Returns a numpy [B] array.
     ``sample_weight``: the prior weights of the local shard's rows
-    (``logistic_loglik_batched`` / ``logistic_loglik_batched_categorical``)."""
-    from .models import logistic_loglik_batched, logistic_loglik_batched_categorical
+    (``logistic_loglik_batched`` / ``logistic_loglik_batched_categorical``).
+    ``family`` = "poisson": the Poisson log-likelihood, with ``eta_offset`` /
+    ``exposure`` of the local shard's rows (``poisson_loglik_batched_weighted``
+    / ``poisson_loglik_batched_categorical``)."""
+    from .models import (logistic_loglik_batched, logistic_loglik_batched_categorical,
+                         poisson_loglik_batched_categorical, poisson_loglik_batched_weighted)
 
-    if codes is not None:
+    if family not in ("logistic", "poisson"):
+        raise ValueError(f"family must be 'logistic' or 'poisson', not {family!r}")
+    if (eta_offset is not None or exposure is not None) and family != "poisson":
+        raise ValueError("eta_offset / exposure need family='poisson'")
+    if family == "poisson":
+        kw = dict(sample_weight=sample_weight, eta_offset=eta_offset, exposure=exposure,
+                  fit_intercept=fit_intercept, center=center, scale=scale, return_sum=True)
+        if codes is not None:
+            _, tot = poisson_loglik_batched_categorical(X, codes, y, offsets, levels, betas, **kw)
+        else:
+            _, tot = poisson_loglik_batched_weighted(X, y, offsets, betas, **kw)
+    elif codes is not None:
         _, tot = logistic_loglik_batched_categorical(
             X, codes, y, offsets, levels, betas, fit_intercept=fit_intercept, center=center,
             scale=scale, return_sum=True, sample_weight=sample_weight)
@@ -122,8 +138,9 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
     categorical-code layout (``logistic_model_batched_categorical``).  The
     row count N of the DBIC is summed in the same single collective as the
     partition sums (reference: the shuffle + collect of dlsa/dlsa.py:30-34).
-    ``family`` = "logistic" or "poisson" (``poisson_model_batched``: dense
-    layout only); everything after the local fits is the same for both.
+    ``family`` = "logistic" or "poisson" (``poisson_model_batched``, with
+    ``codes`` ``poisson_model_batched_categorical``); everything after the
+    local fits is the same for both.
     ``eta_offset`` / ``exposure`` (family="poisson" only): the per-row offset
     of the local shard's rows (``poisson_model_batched_offset``); the combine
     step never sees it.
@@ -138,16 +155,20 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
     from .models import (logistic_model_batched, logistic_model_batched_categorical,
                          logistic_model_batched_categorical_weighted,
                          logistic_model_batched_weighted, poisson_model_batched,
-                         poisson_model_batched_offset, poisson_model_batched_weighted)
+                         poisson_model_batched_categorical, poisson_model_batched_offset,
+                         poisson_model_batched_weighted)
 
     if family not in ("logistic", "poisson"):
         raise ValueError(f"family must be 'logistic' or 'poisson', not {family!r}")
     if (eta_offset is not None or exposure is not None) and family != "poisson":
         raise ValueError("eta_offset / exposure need family='poisson'")
-    if sample_weight is not None:  # (None: exactly the unweighted calls below)
+    if family == "poisson" and codes is not None:
+        fit = poisson_model_batched_categorical(X, codes, y, offsets, levels,
+                                                sample_weight=sample_weight,
+                                                eta_offset=eta_offset, exposure=exposure,
+                                                fit_intercept=fit_intercept, **fit_kw)
+    elif sample_weight is not None:  # (None: exactly the unweighted calls below)
         if family == "poisson":
-            if codes is not None:
-                raise ValueError("family='poisson' runs on the dense layout only (no codes)")
             fit = poisson_model_batched_weighted(X, y, offsets, sample_weight=sample_weight,
                                                  eta_offset=eta_offset, exposure=exposure,
                                                  fit_intercept=fit_intercept, **fit_kw)
@@ -159,8 +180,6 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
             fit = logistic_model_batched_weighted(X, y, offsets, sample_weight=sample_weight,
                                                   fit_intercept=fit_intercept, **fit_kw)
     elif family == "poisson":
-        if codes is not None:
-            raise ValueError("family='poisson' runs on the dense layout only (no codes)")
         if eta_offset is not None or exposure is not None:
             fit = poisson_model_batched_offset(X, y, offsets, eta_offset=eta_offset,
                                                exposure=exposure, fit_intercept=fit_intercept,

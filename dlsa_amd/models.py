@@ -629,6 +629,14 @@ def logistic_model_batched_categorical_weighted(Xn, codes, y, offsets, levels, s
     entry, extras = _entry_and_extras("dlsa_logistic_fit_categorical",
                                       "dlsa_logistic_fit_categorical_weighted", False, None, None,
                                       sample_weight, dev)
+    return _cat_fit(entry, extras, Xd, cd8, yd, offs, lv, cen, sca, fit_intercept, max_iter, tol,
+                    record_timing, rows_per_chunk, zero_partitions, dev)
+
+
+def _cat_fit(entry, extras, Xd, cd8, yd, offs, lv, cen, sca, fit_intercept, max_iter, tol,
+             record_timing, rows_per_chunk, zero_partitions, dev):
+    """The C-ABI call of a fit on the categorical-code layout (``entry`` takes
+    ``extras`` between y and offsets) on ``_cat_inputs``' tensors."""
     q, F, K = Xd.shape[1], cd8.shape[1], offs.size - 1
     P = int(bool(fit_intercept)) + q + int((lv - 1).sum())
     theta, sig, sigt, ll, iters, status = _alloc_outputs(K, P, dev)
@@ -650,6 +658,49 @@ def logistic_model_batched_categorical_weighted(Xn, codes, y, offsets, levels, s
             t[idx] = 0
         status[idx] = 5
     return BatchedFit(theta, sig, sigt, ll, iters, status, offs, bool(fit_intercept), stats)
+
+
+def _pois_cat_extras(entry, Xn, eta_offset, exposure, sample_weight, device):
+    """The argument checks of a Poisson call on the code layout, in their
+    order (Xn 2-D, then the row extras; all before the GPU), then the device
+    and the two tensors ``entry`` takes after y (None: a null pointer)."""
+    if len(_shape(Xn)) != 2:
+        raise ValueError("Xn must be 2-D [n, q]")
+    _check_row_extras(Xn, True, eta_offset, exposure, sample_weight)
+    dev = _require_gpu(device)
+    _, extras = _entry_and_extras(entry, entry, True, eta_offset, exposure, sample_weight, dev)
+    return dev, (extras + [None])[:2]
+
+
+def poisson_model_batched_categorical(Xn, codes, y, offsets, levels, sample_weight=None,
+                                      eta_offset=None, exposure=None, fit_intercept=False,
+                                      center=None, scale=None, max_iter=100, tol=1e-10,
+                                      record_timing=False, rows_per_chunk=0, zero_partitions=None,
+                                      device=None):
+    """Poisson regression (log link) on the categorical-code layout of
+    ``logistic_model_batched_categorical`` (same Xn / codes / levels / center /
+    scale, parameter order, limits and "missing_level" rule): count data with
+    an exposure on a design made of factors, a claim table, without the dummy
+    matrix (``dlsa_poisson_fit_categorical``).
+
+    Per partition exactly ``poisson_model_batched_weighted`` on the
+    dummy-expanded design: ``eta = x . theta + eta_offset``, ``Sig_inv = X^T
+    diag(omega mu) X``, ``loglik = sum omega (y eta - mu - lgamma(y + 1))``.
+    ``eta_offset`` [n] or ``exposure`` [n] > 0 (its log, taken on the device,
+    is the offset) and ``sample_weight`` [n] (finite, >= 0; 0 drops the row)
+    are optional, in any combination, with the ``ValueError`` cases of that
+    function.  Collapsing raw rows to their distinct cells with y = sum y and
+    exposure = sum exposure leaves theta and Sig_inv unchanged.  Statuses: a
+    negative or non-finite y or offset "nonfinite", sum omega y = 0 "singular",
+    a dummy column without a row of omega > 0 "missing_level".  There is no
+    warm-start level for this family on this layout."""
+    dev, extras = _pois_cat_extras("dlsa_poisson_fit_categorical", Xn, eta_offset, exposure,
+                                   sample_weight, device)
+    Xd, cd8, yd, offs, lv, cen, sca = _cat_inputs(Xn, codes, y, offsets, levels, center, scale,
+                                                  dev)
+    return _cat_fit("dlsa_poisson_fit_categorical", extras, Xd, cd8, yd, offs, lv, cen, sca,
+                    fit_intercept, max_iter, tol, record_timing, rows_per_chunk, zero_partitions,
+                    dev)
 
 
 def ols_model_batched(X, y, offsets, fit_intercept=False, center=None, scale=None,
@@ -801,6 +852,14 @@ def logistic_loglik_batched_categorical(Xn, codes, y, offsets, levels, betas, fi
     entry, extras = _entry_and_extras("dlsa_logistic_loglik_categorical",
                                       "dlsa_logistic_loglik_categorical_weighted", False, None,
                                       None, sample_weight, dev)
+    return _cat_loglik(entry, extras, Xd, cd8, yd, offs, lv, cen, sca, betas, fit_intercept,
+                       rows_per_chunk, dev, return_sum)
+
+
+def _cat_loglik(entry, extras, Xd, cd8, yd, offs, lv, cen, sca, betas, fit_intercept,
+                rows_per_chunk, dev, return_sum):
+    """The evaluation pass on the categorical-code layout (``entry`` takes
+    ``extras`` between y and offsets) through ``_loglik_groups``."""
     q, F, K = Xd.shape[1], cd8.shape[1], offs.size - 1
     fn = getattr(_hip.load(), entry)
 
@@ -813,6 +872,24 @@ def logistic_loglik_batched_categorical(Xn, codes, y, offsets, levels, betas, fi
 
     P = int(bool(fit_intercept)) + q + int((lv - 1).sum())
     return _loglik_groups(call, betas, P, K, dev, return_sum)
+
+
+def poisson_loglik_batched_categorical(Xn, codes, y, offsets, levels, betas, sample_weight=None,
+                                       eta_offset=None, exposure=None, fit_intercept=False,
+                                       center=None, scale=None, rows_per_chunk=0, device=None,
+                                       return_sum=False):
+    """``logistic_loglik_batched_categorical`` for the Poisson family, the
+    log-likelihood ``poisson_model_batched_categorical`` returns: per partition
+    and candidate ``sum omega (y eta - exp(eta) - lgamma(y + 1))`` with eta =
+    x . beta + eta_offset on the dummy-expanded design, without building it.
+    ``sample_weight``, ``eta_offset`` / ``exposure`` as there
+    (``dlsa_poisson_loglik_categorical``)."""
+    dev, extras = _pois_cat_extras("dlsa_poisson_loglik_categorical", Xn, eta_offset, exposure,
+                                   sample_weight, device)
+    Xd, cd8, yd, offs, lv, cen, sca = _cat_inputs(Xn, codes, y, offsets, levels, center, scale,
+                                                  dev)
+    return _cat_loglik("dlsa_poisson_loglik_categorical", extras, Xd, cd8, yd, offs, lv, cen, sca,
+                       betas, fit_intercept, rows_per_chunk, dev, return_sum)
 
 
 # ---------------------------------------------------------------------------

@@ -570,6 +570,62 @@ int dlsa_logistic_loglik_categorical_weighted(const double* Xn, const uint8_t* c
                                               double* loglik, double* loglik_sum,
                                               void* stream);
 
+/*
+ * Poisson regression (log link) on the categorical-code layout of
+ * dlsa_logistic_fit_categorical (Xn, codes, levels, parameter order, limits
+ * and the missing-level rule as there): count data with an exposure on a
+ * design made of factors -- a claim table -- from 8 q + F + 8 (+ 8 per row
+ * extra) bytes per row.  Per partition exactly
+ * dlsa_poisson_fit_batched_weighted on the dummy-expanded design: eta = x .
+ * theta + eta_offset, mu = exp(eta), IRLS weight omega mu, sig_inv = X^T
+ * diag(omega mu) X at the returned theta, loglik = sum omega (y eta - mu -
+ * lgamma(y + 1)); the start point log(sum omega y / sum omega e^o) on the
+ * intercept; a step that overshoots is halved.
+ *  eta_offset  [n_total] fp64, device, finite; NULL: none.
+ *  row_weight  [n_total] fp64, device, finite and >= 0 (0 drops the row);
+ *              NULL: none.
+ * Statuses, decided before any Newton pass, each with all-zero outputs: a
+ * negative or non-finite y, eta_offset or omega DLSA_STATUS_NONFINITE; sum
+ * omega = 0 or sum omega y = 0 DLSA_STATUS_SINGULAR; then, among the
+ * partitions still running, a dummy column with no row of omega > 0
+ * DLSA_STATUS_MISSING_LEVEL.  A code >= levels[f] fails the call.
+ * Fixed-point bins: mu has no bound, so the partition's grids are sized on
+ * the device before every pass from an upper bound on its rows' eta at that
+ * pass's theta -- the smaller of an analytic bound (from theta, the columns'
+ * ranges, the largest offset and omega_max) and one measured by the previous
+ * pass (its largest omega mu, moved by the step); the residual's also covers
+ * omega_max y_max: no term can overflow, the result is bit-identical run to run, and the pass
+ * whose Hessian is returned follows a small step, so its grid is tight (bins
+ * within ~1e-13 of an fp64 sum).  A pass for which no grid exists counts as an
+ * overshoot.  opt->warm_start does not apply (a single plan level).
+ */
+int dlsa_poisson_fit_categorical(const double* Xn, const uint8_t* codes, const double* y,
+                                 const double* eta_offset, const double* row_weight,
+                                 const int64_t* offsets, int32_t K, int32_t q, int32_t F,
+                                 const int32_t* levels, int32_t fit_intercept,
+                                 const double* center, const double* scale,
+                                 int32_t max_iter, double tol, double* theta,
+                                 double* sig_inv, double* sig_inv_theta, double* loglik,
+                                 int32_t* iters, int32_t* status,
+                                 const dlsa_fit_options* opt, void* stream);
+
+/*
+ * dlsa_logistic_loglik_categorical for the Poisson family:
+ *   loglik[k * n_beta + b] = sum_i omega_i (y_i eta_i - exp(eta_i) - lgamma(y_i + 1)),
+ * eta_i as there plus eta_offset_i; the value
+ * dlsa_poisson_loglik_batched_sum_weighted gives on the dummy-expanded
+ * design.  eta_offset, row_weight: [n_total] fp64, device, or NULL (o = 0,
+ * omega = 1); neither is checked here.  Same limits and fixed summation order.
+ */
+int dlsa_poisson_loglik_categorical(const double* Xn, const uint8_t* codes, const double* y,
+                                    const double* eta_offset, const double* row_weight,
+                                    const int64_t* offsets, int32_t K, int32_t q, int32_t F,
+                                    const int32_t* levels, int32_t fit_intercept,
+                                    const double* center, const double* scale,
+                                    const double* betas, int32_t n_beta,
+                                    int32_t rows_per_chunk, double* loglik,
+                                    double* loglik_sum, void* stream);
+
 /* Timing/iteration record of the calling thread's last fit. */
 int dlsa_last_fit_stats(dlsa_fit_stats* out);
 

@@ -7,6 +7,10 @@ dlsa/model_eval.py:10-42) through the C-ABI, three legs:
                           (AIRLINE_NUMERIC numeric columns + AIRLINE_FACTORS codes)
   codes_config3_weighted  dlsa_logistic_loglik_categorical_weighted on the same rows with
                           omega ~ U(0.2, 5) (8 more bytes per row); leg name "weighted"
+  codes_config3_poisson   dlsa_poisson_loglik_categorical on the same rows, once per
+                          row-extras mask (none, offset, weights, both: 85 to 101 bytes per
+                          row), betas scaled down so that exp(eta) stays finite; leg name
+                          "poisson"
   dense_expanded_config3  the dense pass on expand_categorical of the same rows: what
                           the evaluation had to read before the code-layout pass
 
@@ -109,6 +113,19 @@ def main():
                 M._ptr(Xn), M._ptr(codes), M._ptr(y), M._ptr(w), off_p, K, q, F, lv_p, 1, None,
                 None, M._ptr(betas), B, 0, M._ptr(out), M._ptr(tot), stream), 8 * q + F + 16)
         del w
+    if "poisson" in want:
+        w = torch.empty(n, dtype=torch.float64, device=dev).uniform_(0.2, 5.0)
+        o = torch.empty(n, dtype=torch.float64, device=dev).uniform_(float(np.log(0.2)),
+                                                                     float(np.log(5.0)))
+        bp = (0.25 * betas).contiguous()
+        for name, om, wm in (("none", None, None), ("offset", o, None), ("weights", None, w),
+                             ("both", o, w)):
+            legs["codes_config3_poisson_" + name], _ = timed(
+                lambda out, tot: lib.dlsa_poisson_loglik_categorical(
+                    M._ptr(Xn), M._ptr(codes), M._ptr(y), M._ptr(om), M._ptr(wm), off_p, K, q, F,
+                    lv_p, 1, None, None, M._ptr(bp), B, 0, M._ptr(out), M._ptr(tot), stream),
+                8 * q + F + 8 + 8 * ((om is not None) + (wm is not None)))
+        del w, o
     if "expanded" in want:
         X = M.expand_categorical(Xn, codes, levels)
         del Xn, codes
