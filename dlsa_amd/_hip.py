@@ -26,6 +26,9 @@ EXACT_AUTO = 0   # exact (Sig_inv) pass on the int8 cores where it applies
 EXACT_FP64 = 1   # exact pass on the fp64 MFMA
 MAX_P_FUSED = 192
 MAX_P = 512
+FAMILY_LOGISTIC = 0  # DLSA_FAMILY_* (the entries that take the family as an argument)
+FAMILY_POISSON = 2
+MAX_GOF_CANDIDATES = 16  # DLSA_MAX_GOF_CANDIDATES: candidates of one goodness-of-fit pass
 
 
 class DlsaHipError(RuntimeError):
@@ -149,6 +152,15 @@ SIGNATURES = {
         ctypes.c_int,
         [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _P, _P,
          _P]),
+    # goodness of fit: the family first, eta_offset and row_weight (either may be null)
+    # after y, beta_part_stride after n_beta; deviance, pearson, n_pos, sums
+    "dlsa_glm_gof_batched": (
+        ctypes.c_int,
+        [_I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _I64, _P, _P, _P, _P, _P]),
+    "dlsa_glm_gof_categorical": (
+        ctypes.c_int,
+        [_I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _I64, _I32,
+         _P, _P, _P, _P, _P]),
     "dlsa_partition_rows": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "dlsa_last_fit_stats": (ctypes.c_int, [ctypes.POINTER(FitStats)]),
     "dlsa_reduce_partitions": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P]),

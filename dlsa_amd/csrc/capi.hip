@@ -252,13 +252,54 @@ int dlsa_logistic_fit_batched(const double* X, const double* y, const int64_t* o
                                       iters, status, nullptr, stream);
 }
 
-// (entry: the name the argument check reports)
+// What a goodness-of-fit call has beside a log-likelihood call's arguments
+// (whose `loglik` is then the deviance and whose `loglik_sum` is null).
+struct GofCall {
+  int64_t beta_part_stride;
+  double* pearson;  // [K, n_beta]
+  double* n_pos;    // [K]
+  double* sums;     // null, or [2 n_beta + 1]: the sums over k of deviance, pearson, n_pos
+};
+// the family, stride and outputs of a goodness-of-fit entry
+static int check_gof(const char* entry, int family, const double* eta_offset, int n_beta, int P,
+                     double* deviance, const GofCall& g) {
+  if (family != FAMILY_LOGISTIC && family != FAMILY_POISSON) {
+    set_error(std::string(entry) + ": family must be DLSA_FAMILY_LOGISTIC or DLSA_FAMILY_POISSON");
+    return DLSA_E_UNSUPPORTED;
+  }
+  if (eta_offset && family != FAMILY_POISSON) {
+    set_error("eta_offset is the Poisson family's");
+    return DLSA_E_INVALID;
+  }
+  if (n_beta < 1 || n_beta > kGofMaxB || !deviance || !g.pearson || !g.n_pos ||
+      !(g.beta_part_stride == 0 || (g.beta_part_stride == P && n_beta == 1))) {
+    set_error(std::string(entry) + ": invalid arguments (1 <= n_beta <= " +
+              std::to_string(kGofMaxB) + ", beta_part_stride 0, or P with n_beta = 1)");
+    return DLSA_E_INVALID;
+  }
+  return DLSA_OK;
+}
+// the three reductions of a goodness-of-fit pass's chunk partials, fixed order
+static hipError_t gof_reduce(const double* d_partial, const GofOut& go, const int32_t* d_pcb, int K,
+                             int B, double* deviance, const GofCall& g, hipStream_t s) {
+  hipError_t e = launch_loglik_reduce(d_partial, d_pcb, K, B, deviance, s);
+  if (e == hipSuccess) e = launch_loglik_reduce(go.partial_chi, d_pcb, K, B, g.pearson, s);
+  if (e == hipSuccess) e = launch_loglik_reduce(go.partial_npos, d_pcb, K, 1, g.n_pos, s);
+  if (e != hipSuccess || !g.sums) return e;
+  e = launch_loglik_total(deviance, K, B, g.sums, s);
+  if (e == hipSuccess) e = launch_loglik_total(g.pearson, K, B, g.sums + B, s);
+  if (e == hipSuccess) e = launch_loglik_total(g.n_pos, K, 1, g.sums + 2 * B, s);
+  return e;
+}
+
+// (entry: the name the argument check reports; gof: the goodness-of-fit pass)
 static int loglik_dense(int family, const char* entry, const double* X, const double* y,
                         const int64_t* offsets, int32_t K, int32_t p, int32_t fit_intercept,
                         const double* center,
                         const double* scale, const double* betas, int32_t n_beta,
                         double* loglik, double* loglik_sum, void* stream_,
-                        const double* eta_offset = nullptr, const double* row_weight = nullptr) {
+                        const double* eta_offset = nullptr, const double* row_weight = nullptr,
+                        const GofCall* gof = nullptr) {
   g_last_error.clear();
   hipStream_t stream = (hipStream_t)stream_;
   int rc = check_offsets(offsets, K);
@@ -268,6 +309,10 @@ static int loglik_dense(int family, const char* entry, const double* X, const do
       (center == nullptr) != (scale == nullptr)) {
     set_error(std::string(entry) + ": invalid arguments (1 <= P <= 512, 1 <= n_beta <= 16)");
     return DLSA_E_INVALID;
+  }
+  if (gof) {
+    rc = check_gof(entry, family, eta_offset, n_beta, P, loglik, *gof);
+    if (rc != DLSA_OK) return rc;
   }
   const int64_t n_total = offsets[K];
   if (n_total > 0 && (!X || !y)) {
@@ -280,6 +325,7 @@ static int loglik_dense(int family, const char* entry, const double* X, const do
   Bump b;
   const int64_t off_row0 = b.take(8 * nc), off_rows = b.take(4 * nc), off_part = b.take(4 * nc);
   const int64_t off_pcb = b.take(4LL * (K + 1)), off_partial = b.take(8 * nc * n_beta);
+  const int64_t off_chi = gof ? b.take(8 * nc * n_beta) : 0, off_npos = gof ? b.take(8 * nc) : 0;
   Workspace ws(stream);
   rc = ws.alloc(b.o);
   if (rc != DLSA_OK) return rc;
@@ -288,10 +334,11 @@ static int loglik_dense(int family, const char* entry, const double* X, const do
   int32_t* d_part = (int32_t*)ws.at(off_part);
   int32_t* d_pcb = (int32_t*)ws.at(off_pcb);
   double* d_partial = (double*)ws.at(off_partial);
+  GofArgs ea;  // (each kernel takes its slice, launch_loglik_eval; launch_gof_eval all of it)
+  memset(&ea, 0, sizeof(ea));
+  if (gof) ea.gof = {(double*)ws.at(off_chi), (double*)ws.at(off_npos), gof->beta_part_stride};
   DLSA_HIP_TRY(upload_eval_plan(pl, K, d_row0, d_rows, d_part, d_pcb, stream));
   if (pl.n_chunks > 0) {
-    EvalArgsWgt ea;  // (each kernel takes its slice, launch_loglik_eval)
-    memset(&ea, 0, sizeof(ea));
     ea.X = X;
     ea.y = y;
     ea.chunk_row0 = d_row0;
@@ -312,10 +359,15 @@ static int loglik_dense(int family, const char* entry, const double* X, const do
     const int PM = ((P + 7) / 8) * 8;
     const int budget = 160 * 1024 - (n_beta * PM + 2 * PM + 64) * 8;
     ea.nslot = std::max(2, std::min(budget / ea.slot_bytes, 6));
-    DLSA_HIP_TRY(launch_loglik_eval(ea, family, pl.n_chunks, stream));
+    DLSA_HIP_TRY(gof ? launch_gof_eval(ea, family, pl.n_chunks, stream)
+                     : launch_loglik_eval(ea, family, pl.n_chunks, stream));
   }
-  DLSA_HIP_TRY(launch_loglik_reduce(d_partial, d_pcb, K, n_beta, loglik, stream));
-  if (loglik_sum) DLSA_HIP_TRY(launch_loglik_total(loglik, K, n_beta, loglik_sum, stream));
+  if (gof) {
+    DLSA_HIP_TRY(gof_reduce(d_partial, ea.gof, d_pcb, K, n_beta, loglik, *gof, stream));
+  } else {
+    DLSA_HIP_TRY(launch_loglik_reduce(d_partial, d_pcb, K, n_beta, loglik, stream));
+    if (loglik_sum) DLSA_HIP_TRY(launch_loglik_total(loglik, K, n_beta, loglik_sum, stream));
+  }
   DLSA_HIP_TRY(hipStreamSynchronize(stream));
   return DLSA_OK;
 }
@@ -392,7 +444,7 @@ static int loglik_categorical(int family, const double* Xn, const uint8_t* codes
                               int32_t q, int32_t F, const int32_t* levels, int32_t fit_intercept,
                               const double* center, const double* scale, const double* betas,
                               int32_t n_beta, int32_t rows_per_chunk, double* loglik,
-                              double* loglik_sum, void* stream_) {
+                              double* loglik_sum, void* stream_, const GofCall* gof = nullptr) {
   g_last_error.clear();
   hipStream_t stream = (hipStream_t)stream_;
   int rc = check_offsets(offsets, K);
@@ -419,7 +471,12 @@ static int loglik_categorical(int family, const double* Xn, const uint8_t* codes
     set_error("eta_offset is the Poisson family's");
     return DLSA_E_INVALID;
   }
-  EvalCatArgsPois ea;  // (every kernel takes its slice: EvalCatArgs, EvalCatArgsWgt or all)
+  if (gof) {
+    rc = check_gof("dlsa_glm_gof_categorical", family, eta_offset, n_beta, P, loglik, *gof);
+    if (rc != DLSA_OK) return rc;
+  }
+  // (every kernel takes its slice: EvalCatArgs, EvalCatArgsWgt, EvalCatArgsPois or all)
+  GofCatArgs ea;
   memset(&ea, 0, sizeof(ea));
   ea.q = q;
   ea.F = F;
@@ -441,6 +498,8 @@ static int loglik_categorical(int family, const double* Xn, const uint8_t* codes
   Bump b;
   const int64_t off_row0 = b.take(8 * nc), off_rows = b.take(4 * nc), off_bad = b.take(4 * nc);
   const int64_t off_pcb = b.take(4LL * (K + 1)), off_partial = b.take(8 * nc * n_beta);
+  const int64_t off_part = gof ? b.take(4 * nc) : 0;  // (only the goodness-of-fit kernels read it)
+  const int64_t off_chi = gof ? b.take(8 * nc * n_beta) : 0, off_npos = gof ? b.take(8 * nc) : 0;
   Workspace ws(stream);
   rc = ws.alloc(b.o);
   if (rc != DLSA_OK) return rc;
@@ -449,7 +508,9 @@ static int loglik_categorical(int family, const double* Xn, const uint8_t* codes
   int32_t* d_bad = (int32_t*)ws.at(off_bad);
   int32_t* d_pcb = (int32_t*)ws.at(off_pcb);
   double* d_partial = (double*)ws.at(off_partial);
-  DLSA_HIP_TRY(upload_eval_plan(pl, K, d_row0, d_rows, nullptr, d_pcb, stream));
+  int32_t* d_part = gof ? (int32_t*)ws.at(off_part) : nullptr;
+  if (gof) ea.gof = {(double*)ws.at(off_chi), (double*)ws.at(off_npos), gof->beta_part_stride};
+  DLSA_HIP_TRY(upload_eval_plan(pl, K, d_row0, d_rows, d_part, d_pcb, stream));
   std::vector<int32_t> h_bad(pl.n_chunks, 0);
   if (pl.n_chunks > 0) {
     ea.Xn = Xn;
@@ -457,6 +518,7 @@ static int loglik_categorical(int family, const double* Xn, const uint8_t* codes
     ea.y = y;
     ea.chunk_row0 = d_row0;
     ea.chunk_rows = d_rows;
+    ea.chunk_part = d_part;
     ea.center = center;
     ea.scale = scale;
     ea.betas = betas;
@@ -475,13 +537,21 @@ static int loglik_categorical(int family, const double* Xn, const uint8_t* codes
     if (row_weight) ea.w_last4 = (uintptr_t)(row_weight + n_total) - 4;
     ea.eta_offset = eta_offset;
     if (eta_offset) ea.o_last4 = (uintptr_t)(eta_offset + n_total) - 4;
-    DLSA_HIP_TRY(pois ? launch_loglik_cat_pois(ea, pl.n_chunks, stream)
-                      : launch_loglik_cat(ea, pl.n_chunks, stream));
+    if (gof)
+      DLSA_HIP_TRY(pois ? launch_gof_cat_pois(ea, pl.n_chunks, stream)
+                        : launch_gof_cat(ea, pl.n_chunks, stream));
+    else
+      DLSA_HIP_TRY(pois ? launch_loglik_cat_pois(ea, pl.n_chunks, stream)
+                        : launch_loglik_cat(ea, pl.n_chunks, stream));
     DLSA_HIP_TRY(hipMemcpyAsync(h_bad.data(), d_bad, 4LL * pl.n_chunks, hipMemcpyDeviceToHost,
                                 stream));
   }
-  DLSA_HIP_TRY(launch_loglik_reduce(d_partial, d_pcb, K, n_beta, loglik, stream));
-  if (loglik_sum) DLSA_HIP_TRY(launch_loglik_total(loglik, K, n_beta, loglik_sum, stream));
+  if (gof) {
+    DLSA_HIP_TRY(gof_reduce(d_partial, ea.gof, d_pcb, K, n_beta, loglik, *gof, stream));
+  } else {
+    DLSA_HIP_TRY(launch_loglik_reduce(d_partial, d_pcb, K, n_beta, loglik, stream));
+    if (loglik_sum) DLSA_HIP_TRY(launch_loglik_total(loglik, K, n_beta, loglik_sum, stream));
+  }
   DLSA_HIP_TRY(hipStreamSynchronize(stream));
   for (int k = 0; k < K; ++k) {
     int64_t nbad = 0;
@@ -530,6 +600,32 @@ int dlsa_poisson_loglik_categorical(const double* Xn, const uint8_t* codes, cons
   return loglik_categorical(FAMILY_POISSON, Xn, codes, y, eta_offset, row_weight, offsets, K, q,
                             F, levels, fit_intercept, center, scale, betas, n_beta,
                             rows_per_chunk, loglik, loglik_sum, stream);
+}
+
+int dlsa_glm_gof_batched(int32_t family, const double* X, const double* y,
+                         const double* eta_offset, const double* row_weight,
+                         const int64_t* offsets, int32_t K, int32_t p, int32_t fit_intercept,
+                         const double* center, const double* scale, const double* betas,
+                         int32_t n_beta, int64_t beta_part_stride, double* deviance,
+                         double* pearson, double* n_pos, double* sums, void* stream) {
+  const GofCall gof{beta_part_stride, pearson, n_pos, sums};
+  return loglik_dense(family, "dlsa_glm_gof_batched", X, y, offsets, K, p, fit_intercept, center,
+                      scale, betas, n_beta, deviance, nullptr, stream, eta_offset, row_weight,
+                      &gof);
+}
+
+int dlsa_glm_gof_categorical(int32_t family, const double* Xn, const uint8_t* codes,
+                             const double* y, const double* eta_offset,
+                             const double* row_weight, const int64_t* offsets, int32_t K,
+                             int32_t q, int32_t F, const int32_t* levels,
+                             int32_t fit_intercept, const double* center, const double* scale,
+                             const double* betas, int32_t n_beta, int64_t beta_part_stride,
+                             int32_t rows_per_chunk, double* deviance, double* pearson,
+                             double* n_pos, double* sums, void* stream) {
+  const GofCall gof{beta_part_stride, pearson, n_pos, sums};
+  return loglik_categorical(family, Xn, codes, y, eta_offset, row_weight, offsets, K, q, F, levels,
+                            fit_intercept, center, scale, betas, n_beta, rows_per_chunk, deviance,
+                            nullptr, stream, &gof);
 }
 
 int dlsa_partition_rows(const int32_t* part_id, int64_t n, int32_t K, int32_t n_arrays,

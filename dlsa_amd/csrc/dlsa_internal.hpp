@@ -411,6 +411,22 @@ template <int EX>
 struct eval_args_of {
   typedef typename std::conditional<(EX & EX_WGT) != 0, EvalArgsWgt, EvalArgs>::type type;
 };
+// Goodness-of-fit pass (gof_pass.hip, gof_cat_pass*.hip): the evaluation pass
+// with two sums per candidate, the deviance (in `partial`) and the Pearson
+// chi-square, and per chunk the count of rows with omega > 0.  Its kernels
+// take these structs of their own, every row-extras mask alike; the
+// log-likelihood kernels keep theirs.  Partition k reads its candidates at
+// betas + k * beta_part_stride: 0, every partition the same [nbeta, P], or P
+// with nbeta = 1, partition k at its own row of a [K, P] matrix.
+constexpr int kGofMaxB = DLSA_MAX_GOF_CANDIDATES;
+struct GofOut {
+  double* partial_chi;   // [n_chunks, nbeta]
+  double* partial_npos;  // [n_chunks]
+  int64_t beta_part_stride;
+};
+struct GofArgs : EvalArgsWgt {
+  GofOut gof;
+};
 
 // Wide-P path (DLSA_MAX_P_FUSED < P <= DLSA_MAX_P, wide_exact.hip): a row
 // pass (eta, weights, gradient, log-lik) and a separate Gram pass over
@@ -581,6 +597,16 @@ hipError_t launch_loglik_cat(const EvalCatArgsWgt& a, int n_chunks, hipStream_t 
 // FAMILY_POISSON: routes on a.eta_offset and a.row_weight
 hipError_t launch_loglik_cat_pois(const EvalCatArgsPois& a, int n_chunks, hipStream_t s);
 hipError_t launch_loglik_total(const double* ll, int K, int B, double* out, hipStream_t s);
+// ... of the goodness-of-fit kernels on this layout (GofArgs above), which
+// also read their chunk's partition
+struct GofCatArgs : EvalCatArgsPois {
+  const int32_t* chunk_part;  // [n_chunks]
+  GofOut gof;
+};
+// route on the family, a.eta_offset and a.row_weight (gof_cat_pass.hip the
+// logistic kernels, gof_cat_pass_pois.hip the Poisson ones)
+hipError_t launch_gof_cat(const GofCatArgs& a, int n_chunks, hipStream_t s);
+hipError_t launch_gof_cat_pois(const GofCatArgs& a, int n_chunks, hipStream_t s);
 
 // Row repartitioning (partition_rows.hip): stable counting sort by partition id.
 constexpr int kPartMaxArrays = 4;
@@ -656,6 +682,8 @@ hipError_t launch_wide_newton(const SolveArgs& sa, const WideArgs& wa, const int
 int wide_newton_lds_bytes(int NB);
 // routes on the row extras; each kernel is handed the slice of EvalArgsWgt it takes
 hipError_t launch_loglik_eval(const EvalArgsWgt& a, int family, int n_chunks, hipStream_t s);
+// the goodness-of-fit pass (gof_pass.hip): the same rules and routing
+hipError_t launch_gof_eval(const GofArgs& a, int family, int n_chunks, hipStream_t s);
 hipError_t launch_loglik_reduce(const double* partial, const int32_t* pcb, int K, int B,
                                 double* out, hipStream_t s);
 int eval_slot_bytes(int p, int n_extras = 0);  // + 256 B per row extra behind y

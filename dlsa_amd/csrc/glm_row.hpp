@@ -61,4 +61,35 @@ __device__ __forceinline__ double row_loglik(double e, double yv, double om, dou
     return om * (yv * e - (fmax(e, 0.0) + log1p(exp(-fabs(e)))));
 }
 
+// One row's terms of the goodness-of-fit passes at eta = e: its deviance and
+// its Pearson chi-square.  What depends on y alone is computed once per row
+// by the caller, rc = row_gof_const(y): the Poisson family's log y (0 at
+// y = 0, where the deviance is 2 omega mu), the logistic family's saturated
+// term y log y + (1 - y) log(1 - y) with 0 log 0 = 0 (0 for 0/1 data, whose
+// deviance is -2 omega l).  y is taken as given (the logistic family's in
+// [0, 1], a grouped row's s / m with omega = m); outside it the terms are NaN.
+struct RowGof { double dev, chi; };
+template <int FAM>
+__device__ __forceinline__ double row_gof_const(double yv) {
+  if constexpr (FAM == FAMILY_POISSON)
+    return yv == 0.0 ? 0.0 : log(yv);
+  else
+    return (yv == 0.0 ? 0.0 : yv * log(yv)) + (yv == 1.0 ? 0.0 : (1.0 - yv) * log1p(-yv));
+}
+// Poisson: d = 2 omega (y (log y - eta) - (y - mu)), chi = omega (y - mu)^2 / mu.
+// Logistic: d = 2 omega (rc - (y eta - softplus(eta))), and with ea = exp(-|eta|)
+// (y - mu)^2 / (mu (1 - mu)) = (y (1 + ea) - [eta >= 0 ? 1 : ea])^2 / ea: 1 - mu
+// is never formed.
+template <int FAM>
+__device__ __forceinline__ RowGof row_gof(double e, double yv, double om, double rc) {
+  if constexpr (FAM == FAMILY_POISSON) {
+    const double mu = exp(e), r = yv - mu;
+    return {2.0 * om * (yv * (rc - e) - r), om * (r * r / mu)};
+  } else {
+    const double ea = exp(-fabs(e));
+    const double t = yv * (1.0 + ea) - (e >= 0.0 ? 1.0 : ea);
+    return {2.0 * om * (rc - (yv * e - (fmax(e, 0.0) + log1p(ea)))), om * (t * t / ea)};
+  }
+}
+
 }  // namespace dlsa

@@ -128,9 +128,65 @@ def loglik_sharded(X, y, offsets, betas, fit_intercept=False, center=None, scale
     return combine(tot, group).cpu().numpy()
 
 
+def gof_sharded(X, y, offsets, betas, fit_intercept=False, center=None, scale=None,
+                codes=None, levels=None, group=None, family="logistic", eta_offset=None,
+                exposure=None, sample_weight=None):
+    """``loglik_sharded`` for the goodness-of-fit pass (``glm_gof_batched`` /
+    ``glm_gof_batched_categorical``, the same arguments): the residual deviance
+    and the Pearson chi-square of each candidate row of ``betas`` [B, P] over
+    the whole data set, and the rows with a positive weight.  ONE all-reduce of
+    this rank's 2B + 1 totals.  Returns a dict, the same on every rank:
+    ``deviance`` and ``pearson`` numpy [B], ``n_pos`` an int."""
+    import torch
+
+    from .models import glm_gof_batched, glm_gof_batched_categorical
+
+    kw = dict(betas=betas, eta_offset=eta_offset, exposure=exposure, sample_weight=sample_weight,
+              fit_intercept=fit_intercept, center=center, scale=scale, return_sum=True)
+    if codes is not None:
+        g = glm_gof_batched_categorical(family, X, codes, y, offsets, levels, **kw)
+    else:
+        g = glm_gof_batched(family, X, y, offsets, **kw)
+    B = g["deviance_sum"].numel()
+    tot = torch.cat([g["deviance_sum"], g["pearson_sum"],
+                     g["n_pos_sum"].to(torch.float64).reshape(1)])
+    tot = combine(tot, group).cpu().numpy()
+    return {"deviance": tot[:B], "pearson": tot[B:2 * B], "n_pos": int(round(float(tot[-1])))}
+
+
+def _pearson_dispersion(fit, X, y, offsets, codes, levels, family, eta_offset, exposure,
+                        sample_weight, fit_intercept, center, scale, group):
+    """phi = sum_k chi^2_k / (sum_k n+_k - K_ok P): the Pearson chi-square of
+    every partition at its own ``fit.theta`` row (one goodness-of-fit pass in
+    per-partition mode) over the residual degrees of freedom, summed over the
+    partitions the combine counts (status ok or maxiter; K_ok of them) and over
+    the ranks (one all-reduce of three doubles)."""
+    import torch
+
+    from .models import glm_gof_batched, glm_gof_batched_categorical
+
+    kw = dict(thetas=fit.theta, eta_offset=eta_offset, exposure=exposure,
+              sample_weight=sample_weight, fit_intercept=fit_intercept, center=center,
+              scale=scale)
+    if codes is not None:
+        g = glm_gof_batched_categorical(family, X, codes, y, offsets, levels, **kw)
+    else:
+        g = glm_gof_batched(family, X, y, offsets, **kw)
+    ok = fit.status <= 1
+    zero = torch.zeros((), dtype=torch.float64, device=ok.device)
+    chi = torch.where(ok, g["pearson"][:, 0], zero).sum()
+    npos = torch.where(ok, g["n_pos"].to(torch.float64), zero).sum()
+    tot = combine(torch.stack([chi, npos, ok.sum().to(torch.float64)]), group).cpu().numpy()
+    dof = tot[1] - tot[2] * fit.P
+    if not dof > 0:
+        raise ValueError(f"dispersion='pearson': residual degrees of freedom {dof:g} = rows with "
+                         "a positive weight - fitted partitions x P is not positive")
+    return float(tot[0] / dof)
+
+
 def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
                      group=None, codes=None, levels=None, family="logistic", eta_offset=None,
-                     exposure=None, sample_weight=None, **fit_kw):
+                     exposure=None, dispersion=None, sample_weight=None, **fit_kw):
     """Fit this rank's partitions on its GPU and return the global DLSA result.
 
     X, y, offsets describe the LOCAL shard (rows already on this rank's
@@ -151,6 +207,15 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
     precision or survey weights leave the number of observations unchanged.  A
     frequency-weights user who wants N = sum of the weights calls
     ``finish(..., n_global=)`` on the reduced sums directly.
+    ``dispersion``: None (the default: exactly the call without the keyword),
+    or "pearson", the quasi-likelihood correction of an over-dispersed fit (R's
+    quasipoisson / quasibinomial): after the local fits one goodness-of-fit
+    pass at each partition's own ``fit.theta`` and one more all-reduce of
+    three doubles give phi = Pearson chi^2 / residual degrees of freedom
+    (``_pearson_dispersion``), and the tail runs on ``S / phi``, ``v / phi``.
+    The WLSE is unchanged; LARS / DBIC see the scaled information matrix.  The
+    result gains ``"dispersion"``.  Non-positive degrees of freedom raise
+    ``ValueError``.
     """
     from .models import (logistic_model_batched, logistic_model_batched_categorical,
                          logistic_model_batched_categorical_weighted,
@@ -162,6 +227,8 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
         raise ValueError(f"family must be 'logistic' or 'poisson', not {family!r}")
     if (eta_offset is not None or exposure is not None) and family != "poisson":
         raise ValueError("eta_offset / exposure need family='poisson'")
+    if dispersion not in (None, "pearson"):
+        raise ValueError(f"dispersion must be None or 'pearson', not {dispersion!r}")
     if family == "poisson" and codes is not None:
         fit = poisson_model_batched_categorical(X, codes, y, offsets, levels,
                                                 sample_weight=sample_weight,
@@ -192,6 +259,15 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
     else:
         fit = logistic_model_batched(X, y, offsets, fit_intercept=fit_intercept, **fit_kw)
     buf = reduce_partitions_device(fit, n_rows=True)
-    out = combine_and_finish(buf, fit.P, fit_intercept, lars_type, group)
+    if dispersion is None:
+        out = combine_and_finish(buf, fit.P, fit_intercept, lars_type, group)
+    else:
+        phi = _pearson_dispersion(fit, X, y, offsets, codes, levels, family, eta_offset, exposure,
+                                  sample_weight, fit_intercept, fit_kw.get("center"),
+                                  fit_kw.get("scale"), group)
+        b = combine(buf, group).cpu().numpy()
+        S, v, st, K = split_reduced(b[:-1], fit.P)
+        out = finish(S / phi, v / phi, st, K, int(round(float(b[-1]))), fit_intercept, lars_type)
+        out["dispersion"] = phi
     out["fit"] = fit
     return out

@@ -893,6 +893,142 @@ def poisson_loglik_batched_categorical(Xn, codes, y, offsets, levels, betas, sam
 
 
 # ---------------------------------------------------------------------------
+# goodness of fit: deviance, Pearson chi-square, rows with a positive weight
+# ---------------------------------------------------------------------------
+
+MAX_GOF_CANDIDATES = _hip.MAX_GOF_CANDIDATES  # candidates of one goodness-of-fit pass
+_GOF_FAMILIES = {"logistic": _hip.FAMILY_LOGISTIC, "poisson": _hip.FAMILY_POISSON}
+
+
+def _check_gof_args(family, X, betas, thetas, eta_offset, exposure, sample_weight):
+    """The argument checks of a goodness-of-fit call that need no GPU; returns
+    the family's code."""
+    if family not in _GOF_FAMILIES:
+        raise ValueError(f"family must be 'logistic' or 'poisson', not {family!r}")
+    if (betas is None) == (thetas is None):
+        raise ValueError("give exactly one of betas [B, P] (the same candidates for every "
+                         "partition) and thetas [K, P] (each partition at its own row)")
+    if len(_shape(X)) != 2:
+        raise ValueError("X must be 2-D [n, p]")
+    if family != "poisson" and (eta_offset is not None or exposure is not None):
+        raise ValueError("eta_offset / exposure need family='poisson'")
+    _check_row_extras(X, family == "poisson", eta_offset, exposure, sample_weight)
+    return _GOF_FAMILIES[family]
+
+
+def _gof_groups(call, betas, thetas, P, K, dev, return_sum):
+    """Run ``call(coef, g, stride, deviance [K, g], pearson [K, g], n_pos [K],
+    sums [2g + 1])`` and assemble the result dict.  ``betas`` [B, P]: in
+    groups of at most ``MAX_GOF_CANDIDATES`` (one pass over the data each,
+    stride 0).  ``thetas`` [K, P]: one pass, B = 1, partition k at row k."""
+    f64 = dict(dtype=torch.float64, device=dev)
+    cd = _dev_f64(betas if thetas is None else thetas, dev)
+    if cd.dim() == 1:
+        cd = cd.reshape(1, -1)
+    if thetas is not None:
+        if cd.dim() != 2 or tuple(cd.shape) != (K, P):
+            raise ValueError("thetas must be [K, P]: one row per partition")
+        B = 1
+    elif cd.dim() != 2 or cd.shape[0] < 1 or cd.shape[1] != P:
+        raise ValueError("betas must be [B, P] with B >= 1 and P = the design's parameters")
+    else:
+        B = cd.shape[0]
+    dv, ch = torch.empty((K, B), **f64), torch.empty((K, B), **f64)
+    npos = torch.empty((K,), **f64)
+    tot = torch.empty((2, B), **f64)
+    for b0 in range(0, B, MAX_GOF_CANDIDATES):
+        g = min(MAX_GOF_CANDIDATES, B - b0)
+        whole = g == B
+        d, c = (dv, ch) if whole else (torch.empty((K, g), **f64), torch.empty((K, g), **f64))
+        sums = torch.empty((2 * g + 1,), **f64)
+        coef = cd.contiguous() if thetas is not None else cd[b0:b0 + g].contiguous()
+        call(coef, g, P if thetas is not None else 0, d, c, npos, sums)
+        if not whole:
+            dv[:, b0:b0 + g], ch[:, b0:b0 + g] = d, c
+        tot[0, b0:b0 + g], tot[1, b0:b0 + g] = sums[:g], sums[g:2 * g]
+    out = {"deviance": dv, "pearson": ch, "n_pos": npos.to(torch.int64)}
+    if return_sum:
+        out.update(deviance_sum=tot[0], pearson_sum=tot[1], n_pos_sum=sums[-1].to(torch.int64))
+    return out
+
+
+def glm_gof_batched(family, X, y, offsets, betas=None, thetas=None, eta_offset=None,
+                    exposure=None, sample_weight=None, fit_intercept=False, center=None,
+                    scale=None, device=None, return_sum=False):
+    """Goodness of fit of a GLM in one more pass over X (the bytes per row of
+    ``*_loglik_batched``): per partition and candidate the residual deviance
+    and the Pearson chi-square, per partition the rows with a positive weight
+    (``dlsa_glm_gof_batched``).  ``family``: "logistic" or "poisson".
+
+    Exactly one of ``betas`` [B, P] (every partition at the same candidates:
+    the job-level deviance of the combined or selected estimates; more than
+    ``MAX_GOF_CANDIDATES`` are evaluated in groups) and ``thetas`` [K, P]
+    (partition k at its own row, "at the fit's own theta_k", B = 1: what the
+    degrees of freedom of the dispersion estimate chi^2 / (n - P) assume).
+    ``eta_offset`` / ``exposure`` (Poisson only) and ``sample_weight`` as in
+    the fits, with their ``ValueError`` cases.  The logistic y is taken as
+    given in [0, 1], so grouped rows y = s / m with weight m work; it is not
+    checked, and outside [0, 1] the sums are NaN.
+
+    Returns a dict of device tensors: ``deviance`` [K, B], ``pearson`` [K, B]
+    (fp64), ``n_pos`` [K] (int64); with ``return_sum`` also their sums over the
+    partitions, ``deviance_sum`` [B], ``pearson_sum`` [B], ``n_pos_sum``.
+    Fixed summation order: two calls give the same bits."""
+    fam = _check_gof_args(family, X, betas, thetas, eta_offset, exposure, sample_weight)
+    dev, Xd, yd, offs, cd, sd = _dense_inputs(X, y, offsets, center, scale, device)
+    od, wd = _gof_extras(family, eta_offset, exposure, sample_weight, dev)
+    p, K = Xd.shape[1], offs.size - 1
+    fn = _hip.load().dlsa_glm_gof_batched
+
+    def call(coef, g, stride, d, c, npos, sums):
+        rc = fn(fam, _ptr(Xd), _ptr(yd), _ptr(od), _ptr(wd), offs.ctypes.data_as(ctypes.c_void_p),
+                K, p, int(bool(fit_intercept)), _ptr(cd), _ptr(sd), _ptr(coef), g, stride,
+                _ptr(d), _ptr(c), _ptr(npos), _ptr(sums), _stream(dev))
+        _hip.check(rc, "dlsa_glm_gof_batched")
+
+    return _gof_groups(call, betas, thetas, p + (1 if fit_intercept else 0), K, dev, return_sum)
+
+
+def _gof_extras(family, eta_offset, exposure, sample_weight, dev):
+    """The device offset and weight of a goodness-of-fit call (None: a null
+    pointer)."""
+    _, extras = _entry_and_extras(None, None, family == "poisson", eta_offset, exposure,
+                                  sample_weight, dev)
+    od = extras[0] if family == "poisson" else None
+    wd = extras[-1] if sample_weight is not None else None
+    return od, wd
+
+
+def glm_gof_batched_categorical(family, Xn, codes, y, offsets, levels, betas=None, thetas=None,
+                                eta_offset=None, exposure=None, sample_weight=None,
+                                fit_intercept=False, center=None, scale=None, rows_per_chunk=0,
+                                device=None, return_sum=False):
+    """``glm_gof_batched`` on the categorical-code layout of
+    ``logistic_model_batched_categorical`` (same Xn / codes / levels / center /
+    scale and parameter order): the deviance and Pearson chi-square of the
+    dummy-expanded design without building it, the dummy coefficients a table
+    in LDS (``dlsa_glm_gof_categorical``).  A code >= levels[f] raises
+    ``DlsaHipError``."""
+    fam = _check_gof_args(family, Xn, betas, thetas, eta_offset, exposure, sample_weight)
+    dev = _require_gpu(device)
+    Xd, cd8, yd, offs, lv, cen, sca = _cat_inputs(Xn, codes, y, offsets, levels, center, scale,
+                                                  dev)
+    od, wd = _gof_extras(family, eta_offset, exposure, sample_weight, dev)
+    q, F, K = Xd.shape[1], cd8.shape[1], offs.size - 1
+    fn = _hip.load().dlsa_glm_gof_categorical
+
+    def call(coef, g, stride, d, c, npos, sums):
+        rc = fn(fam, _ptr(Xd), _ptr(cd8), _ptr(yd), _ptr(od), _ptr(wd),
+                offs.ctypes.data_as(ctypes.c_void_p), K, q, F, lv.ctypes.data_as(ctypes.c_void_p),
+                int(bool(fit_intercept)), _ptr(cen), _ptr(sca), _ptr(coef), g, stride,
+                int(rows_per_chunk), _ptr(d), _ptr(c), _ptr(npos), _ptr(sums), _stream(dev))
+        _hip.check(rc, "dlsa_glm_gof_categorical")
+
+    P = int(bool(fit_intercept)) + q + int((lv - 1).sum())
+    return _gof_groups(call, betas, thetas, P, K, dev, return_sum)
+
+
+# ---------------------------------------------------------------------------
 # reference-signature wrapper (one Spark group)
 # ---------------------------------------------------------------------------
 

@@ -101,6 +101,13 @@ extern "C" {
                                  128x128-tiled Gram pass and a blocked Cholesky in HBM
                                  take over (BASELINE config 5, p = 500) */
 
+/* The families the entries that take one as an argument know (dlsa_glm_gof_*). */
+#define DLSA_FAMILY_LOGISTIC 0
+#define DLSA_FAMILY_POISSON 2
+/* Candidates of one goodness-of-fit pass: the most at which none of its
+   kernels spills (two sums per candidate). */
+#define DLSA_MAX_GOF_CANDIDATES 16
+
 typedef struct dlsa_fit_options {
   int32_t hessian_mode;     /* DLSA_HESSIAN_MIXED (default) or _FP64 */
   int32_t record_timing;    /* 1: time every launch with hipEvents, see
@@ -625,6 +632,55 @@ int dlsa_poisson_loglik_categorical(const double* Xn, const uint8_t* codes, cons
                                     const double* betas, int32_t n_beta,
                                     int32_t rows_per_chunk, double* loglik,
                                     double* loglik_sum, void* stream);
+
+/*
+ * Goodness of fit of candidate coefficient vectors, one more evaluation pass
+ * (the bytes per row, limits and scratch handling of the log-likelihood entry
+ * of the same layout and row extras).  family: DLSA_FAMILY_LOGISTIC or
+ * DLSA_FAMILY_POISSON, any other DLSA_E_UNSUPPORTED.  With mu_i the mean at
+ * eta_i = x_i . beta (+ eta_offset_i) and omega_i the prior weight:
+ *   deviance[k * n_beta + b] = sum_i d_i,   pearson[k * n_beta + b] = sum_i chi_i
+ *   n_pos[k] = the rows of partition k with omega_i > 0 (all of them without
+ *              weights), an exact integer in fp64
+ *   Poisson:  d = 2 omega (y log(y / mu) - (y - mu)) (2 omega mu at y = 0),
+ *             chi = omega (y - mu)^2 / mu
+ *   logistic: d = 2 omega (y log y + (1 - y) log(1 - y) - (y eta - log(1 + exp(eta)))),
+ *             0 log 0 = 0 (-2 omega l for 0/1 data),
+ *             chi = omega (y - mu)^2 / (mu (1 - mu));
+ *             y is taken as given in [0, 1] (a grouped row: y = s / m, omega =
+ *             m) and not checked: outside it the sums are NaN.
+ * eta_offset, row_weight: [n_total] fp64, device, or NULL; an offset with the
+ * logistic family is DLSA_E_INVALID.  Neither is checked here.
+ * betas, beta_part_stride: partition k is evaluated at the [n_beta, P] matrix
+ * at betas + k * beta_part_stride -- 0: the same candidates for every
+ * partition; P with n_beta = 1: betas is [K, P], each partition at its own
+ * row (its own estimate).  Any other stride is DLSA_E_INVALID.
+ * 1 <= n_beta <= DLSA_MAX_GOF_CANDIDATES.
+ * sums: NULL, or [2 n_beta + 1] device: the sums over k of deviance, of
+ * pearson and of n_pos, in that order.  Fixed summation order throughout: two
+ * calls give the same bits.
+ */
+int dlsa_glm_gof_batched(int32_t family, const double* X, const double* y,
+                         const double* eta_offset, const double* row_weight,
+                         const int64_t* offsets, int32_t K, int32_t p, int32_t fit_intercept,
+                         const double* center, const double* scale, const double* betas,
+                         int32_t n_beta, int64_t beta_part_stride, double* deviance,
+                         double* pearson, double* n_pos, double* sums, void* stream);
+
+/*
+ * dlsa_glm_gof_batched on the categorical-code layout of
+ * dlsa_logistic_loglik_categorical (its arguments, limits and error cases: a
+ * code >= levels[f] fails the call with DLSA_E_INVALID): the values the dense
+ * entry gives on the dummy-expanded design.
+ */
+int dlsa_glm_gof_categorical(int32_t family, const double* Xn, const uint8_t* codes,
+                             const double* y, const double* eta_offset,
+                             const double* row_weight, const int64_t* offsets, int32_t K,
+                             int32_t q, int32_t F, const int32_t* levels,
+                             int32_t fit_intercept, const double* center, const double* scale,
+                             const double* betas, int32_t n_beta, int64_t beta_part_stride,
+                             int32_t rows_per_chunk, double* deviance, double* pearson,
+                             double* n_pos, double* sums, void* stream);
 
 /* Timing/iteration record of the calling thread's last fit. */
 int dlsa_last_fit_stats(dlsa_fit_stats* out);
