@@ -283,10 +283,13 @@ void irls_coop_kernel(const typename pass_args_of<EX>::type a) {
     if constexpr (CM & 1) cmx[m] = 0u;
     if constexpr (CM & 2) zmx[m] = 0.0f;
   }
-  int tI[G::TPW], tJ[G::TPW];  // this wave's tiles (bf16 path)
+  // this wave's tiles (bf16 path).  The last wave's surplus entries (t >= T)
+  // name tile T - 1 again: the tile phase runs them like the others, without
+  // a branch, into accumulators that store_tiles never writes out
+  int tI[G::TPW], tJ[G::TPW];
 #pragma unroll
   for (int i = 0; i < G::TPW; ++i) {
-    const int t = wid * G::TPW + i;
+    const int t = min(wid * G::TPW + i, G::T - 1);
     int I = 0;
     while ((I + 1) * (I + 2) / 2 <= t) ++I;
     tI[i] = __builtin_amdgcn_readfirstlane(I);
@@ -487,16 +490,21 @@ void irls_coop_kernel(const typename pass_args_of<EX>::type a) {
       if constexpr (PREC == PREC_BF16) {
         // one code path for every wave: the wave's tile indices are
         // wave-uniform registers (no per-wave copies of the loop body, whose
-        // merge would copy the accumulators every block)
+        // merge would copy the accumulators every block), and no branch per
+        // tile: straight-line code, so the operand reads of all the wave's
+        // tiles are issued ahead of the MFMAs instead of one LDS round trip
+        // per tile -- the tile phase sits in the workgroup's serial chain
+        // B1, row phase, B2, tile phase
         const int fl = lane & 15, q = lane >> 4;
+        bf16x8 Av[G::TPW], Bv[G::TPW];
 #pragma unroll
         for (int i = 0; i < G::TPW; ++i) {
-          if (wid * G::TPW + i < G::T) {  // wave-uniform
-            const bf16x8 Av = *(const bf16x8*)(obx + (16 * tI[i] + fl) * G::OBS + 8 * q);
-            const bf16x8 Bv = *(const bf16x8*)(obx + (16 * tJ[i] + fl) * G::OBS + 8 * q);
-            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Av, Bv, acc[i], 0, 0, 0);
-          }
+          Av[i] = *(const bf16x8*)(obx + (16 * tI[i] + fl) * G::OBS + 8 * q);
+          Bv[i] = *(const bf16x8*)(obx + (16 * tJ[i] + fl) * G::OBS + 8 * q);
         }
+#pragma unroll
+        for (int i = 0; i < G::TPW; ++i)
+          acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Av[i], Bv[i], acc[i], 0, 0, 0);
       } else {
         static_for<W>([&](auto wI) {
           constexpr int WID = decltype(wI)::value;
