@@ -112,8 +112,9 @@ inline Fn* find_unit(const UnitRow<Fn> (&table)[N], int family, int extras, int 
 
 // Cache policy of the LDS-DMA loads that stream X (the aux / cpol operand of
 // buffer_load ... lds; profiling builds override it, tools/build_variants.sh).
-// The cooperative and per-wave passes keep the default policy: with nt (2)
-// the lines their consecutive blocks share are fetched twice (PMC, run r04g:
+// The cooperative (but see DLSA_COOP_NT7_DMA_AUX) and per-wave passes keep
+// the default policy: with nt (2) the lines their consecutive blocks share
+// are fetched twice (PMC, run r04g:
 // 842.6 vs 812.4 B/row for the config-2 bf16 pass, 624 vs 523 B/row for the
 // config-4 OLS pass, whose blocks are 8 rows); the Ozaki exact pass streams
 // non-temporally (813.6 vs 812.4 B/row, 17.6-18.0 vs 17.9-18.1 ms at config
@@ -123,6 +124,16 @@ inline Fn* find_unit(const UnitRow<Fn> (&table)[N], int family, int extras, int 
 #endif
 #ifndef DLSA_OZ_DMA_AUX
 #define DLSA_OZ_DMA_AUX 2
+#endif
+// The bf16 cooperative pass at NT = 7 (96 < P <= 112, the flagship's shape: a
+// two-slot ring, one block in flight per workgroup) streams non-temporally as
+// well: the re-fetched shared lines cost less than the policy gains there,
+// 13.21-13.22 -> 12.91-12.93 ms per full config-2 pass in interleaved rounds.
+// At the other shapes measured (p = 16, 50, 120, 140: deeper rings, one
+// workgroup per CU or eight waves) nt is level or slower, up to +0.6 ms at
+// p = 140, so they keep the default (profiles/r08a_coop_pipeline_ab.txt).
+#ifndef DLSA_COOP_NT7_DMA_AUX
+#define DLSA_COOP_NT7_DMA_AUX 2
 #endif
 // Cooperative pass: 4 (8) waves per workgroup, 32-row blocks.
 constexpr int kCoopRows = 32;

@@ -16,7 +16,8 @@
 //   B   row phase: rows split over the waves, 8 lanes per row.  eta = x.theta
 //       (fp64, 8-lane DPP reduction), mu, w = mu(1-mu), r = y - mu, the
 //       gradient x*r and the log-likelihood are computed ONCE per row; w and r
-//       are published in LDS.
+//       are published in LDS (PREC_F32 / PREC_F64; the bf16 tiles read only the
+//       operand image the row phase writes).
 //   B2  barrier.
 //   C   tile phase: the lower-triangle 16x16 tiles of X^T W X are split over
 //       the waves (contiguous tile ranges, so each wave touches few column
@@ -342,7 +343,7 @@ void irls_coop_kernel(const typename pass_args_of<EX>::type a) {
       const int jj = j < npieces ? j : npieces - 1;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
           xr_rsrc, (lds_void_t*)(sbase + G::PAD + jj * 1024), 16, vx, so + jj * 1024, 0,
-          DLSA_X_DMA_AUX);
+          (PREC == PREC_BF16 && NT == 7) ? DLSA_COOP_NT7_DMA_AUX : DLSA_X_DMA_AUX);
     }
     __builtin_amdgcn_raw_ptr_buffer_load_lds(yr_rsrc, (lds_void_t*)(sbase + slot_x), 4, vy,
                                              bb * RB * 8, 0, 0);
@@ -456,9 +457,11 @@ void irls_coop_kernel(const typename pass_args_of<EX>::type a) {
       }
 #pragma unroll
       for (int m = 0; m < M; ++m) gacc[m] = fma(xv[m], r, gacc[m]);
-      if (sl == 0) {
-        wr[rB] = w;
-        wr[RB + rB] = r;
+      if constexpr (PREC != PREC_BF16) {  // the bf16 tiles read the image alone
+        if (sl == 0) {
+          wr[rB] = w;
+          wr[RB + rB] = r;
+        }
       }
       if constexpr (PREC == PREC_BF16) {
         // stage the bf16 MFMA operand z = sqrt(w) x once per row; one

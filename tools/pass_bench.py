@@ -138,6 +138,7 @@ def main():
                 m = statistics.median(d[key])
                 out[f"{key}_ms"] = round(m, 3)
                 out[f"{key}_GBps"] = round(bytes_per_pass / (m * 1e-3) / 1e9, 1)
+                out[f"{key}_ms_rounds"] = [round(v, 3) for v in d[key]]  # the spread
         out["solve_ms_per_iter"] = round(statistics.median(d["solve"]), 3)
         out["fit_ms"] = round(statistics.median(d["total"]), 2)
         if d.get("prof"):
