@@ -29,6 +29,8 @@ MAX_P = 512
 FAMILY_LOGISTIC = 0  # DLSA_FAMILY_* (the entries that take the family as an argument)
 FAMILY_POISSON = 2
 MAX_GOF_CANDIDATES = 16  # DLSA_MAX_GOF_CANDIDATES: candidates of one goodness-of-fit pass
+GRAM_SCORE = 0        # DLSA_GRAM_*: the row weight of dlsa_glm_gram_batched's Gram
+GRAM_INFORMATION = 1
 
 
 class DlsaHipError(RuntimeError):
@@ -161,6 +163,16 @@ SIGNATURES = {
         ctypes.c_int,
         [_I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _I64, _I32,
          _P, _P, _P, _P, _P]),
+    # score outer products: family, kind; eta_offset and row_weight after y; the stride
+    # after betas; gram, score, gram_sum, score_sum (the chunked entry: rows_per_chunk
+    # after the stride)
+    "dlsa_glm_gram_batched": (
+        ctypes.c_int,
+        [_I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    "dlsa_glm_gram_batched_chunked": (
+        ctypes.c_int,
+        [_I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _I32, _P, _P, _P, _P,
+         _P]),
     "dlsa_partition_rows": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "dlsa_last_fit_stats": (ctypes.c_int, [ctypes.POINTER(FitStats)]),
     "dlsa_reduce_partitions": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P]),

@@ -614,6 +614,114 @@ int dlsa_glm_gof_batched(int32_t family, const double* X, const double* y,
                       &gof);
 }
 
+static int gram_dense(int32_t family, int32_t kind, const double* X, const double* y,
+                      const double* eta_offset, const double* row_weight, const int64_t* offsets,
+                      int32_t K, int32_t p, int32_t fit_intercept, const double* center,
+                      const double* scale, const double* betas, int64_t beta_part_stride,
+                      int32_t rows_per_chunk, double* gram, double* score, double* gram_sum,
+                      double* score_sum, void* stream_) {
+  g_last_error.clear();
+  hipStream_t stream = (hipStream_t)stream_;
+  int rc = check_offsets(offsets, K);
+  if (rc != DLSA_OK) return rc;
+  if (family != FAMILY_LOGISTIC && family != FAMILY_POISSON) {
+    set_error("dlsa_glm_gram_batched: family must be DLSA_FAMILY_LOGISTIC or DLSA_FAMILY_POISSON");
+    return DLSA_E_UNSUPPORTED;
+  }
+  const int P = p + (fit_intercept ? 1 : 0);
+  if (p < 0 || P < 1 || rows_per_chunk < 0 || !betas || !gram || !score ||
+      (kind != GRAM_SCORE && kind != GRAM_INFORMATION) ||
+      (center == nullptr) != (scale == nullptr)) {
+    set_error("dlsa_glm_gram_batched: invalid arguments (P >= 1, kind DLSA_GRAM_SCORE or "
+              "DLSA_GRAM_INFORMATION, center and scale both or neither)");
+    return DLSA_E_INVALID;
+  }
+  if (P > DLSA_MAX_P_FUSED) {  // before any launch
+    set_error("dlsa_glm_gram_batched: P = p + intercept > DLSA_MAX_P_FUSED = " +
+              std::to_string(DLSA_MAX_P_FUSED) + " is not supported");
+    return DLSA_E_UNSUPPORTED;
+  }
+  if (eta_offset && family != FAMILY_POISSON) {
+    set_error("eta_offset is the Poisson family's");
+    return DLSA_E_INVALID;
+  }
+  if (beta_part_stride != 0 && beta_part_stride != P) {
+    set_error("dlsa_glm_gram_batched: beta_part_stride must be 0 or P");
+    return DLSA_E_INVALID;
+  }
+  const int64_t n_total = offsets[K];
+  if (n_total > 0 && (!X || !y)) {
+    set_error("null X or y");
+    return DLSA_E_INVALID;
+  }
+  Plan pl;
+  make_plan(offsets, K, p, fit_intercept, rows_per_chunk, pl);
+  const int64_t nc = std::max(pl.n_chunks, 1);
+  Bump b;
+  const int64_t off_row0 = b.take(8 * nc), off_rows = b.take(4 * nc), off_part = b.take(4 * nc);
+  const int64_t off_pcb = b.take(4LL * (K + 1));
+  const int64_t off_G = b.take(8 * nc * pl.T * 256), off_s = b.take(8 * nc * pl.PP);
+  Workspace ws(stream);
+  rc = ws.alloc(b.o);
+  if (rc != DLSA_OK) return rc;
+  int64_t* d_row0 = (int64_t*)ws.at(off_row0);
+  int32_t* d_rows = (int32_t*)ws.at(off_rows);
+  int32_t* d_part = (int32_t*)ws.at(off_part);
+  int32_t* d_pcb = (int32_t*)ws.at(off_pcb);
+  GramArgs ga;
+  memset(&ga, 0, sizeof(ga));
+  ga.P = P;
+  ga.slab_G = (double*)ws.at(off_G);
+  ga.slab_s = (double*)ws.at(off_s);
+  DLSA_HIP_TRY(upload_eval_plan(pl, K, d_row0, d_rows, d_part, d_pcb, stream));
+  if (pl.n_chunks > 0) {
+    ga.X = X;
+    ga.y = y;
+    ga.chunk_row0 = d_row0;
+    ga.chunk_rows = d_rows;
+    ga.chunk_part = d_part;
+    ga.center = center;
+    ga.scale = scale;
+    ga.betas = betas;
+    ga.eta_offset = eta_offset;
+    ga.row_weight = row_weight;
+    ga.p = p;
+    set_stream_bounds(ga, n_total);
+    ga.intercept = fit_intercept ? 1 : 0;
+    ga.nbeta = 1;
+    ga.beta_part_stride = beta_part_stride;
+    ga.kind = kind;
+    DLSA_HIP_TRY(launch_score_pass(ga, family, pl.n_chunks, stream));
+  }
+  DLSA_HIP_TRY(launch_gram_reduce(ga, d_pcb, K, gram, score, gram_sum, score_sum, stream));
+  DLSA_HIP_TRY(hipStreamSynchronize(stream));
+  return DLSA_OK;
+}
+
+int dlsa_glm_gram_batched(int32_t family, int32_t kind, const double* X, const double* y,
+                          const double* eta_offset, const double* row_weight,
+                          const int64_t* offsets, int32_t K, int32_t p, int32_t fit_intercept,
+                          const double* center, const double* scale, const double* betas,
+                          int64_t beta_part_stride, double* gram, double* score,
+                          double* gram_sum, double* score_sum, void* stream) {
+  return gram_dense(family, kind, X, y, eta_offset, row_weight, offsets, K, p, fit_intercept,
+                    center, scale, betas, beta_part_stride, 0, gram, score, gram_sum, score_sum,
+                    stream);
+}
+
+int dlsa_glm_gram_batched_chunked(int32_t family, int32_t kind, const double* X, const double* y,
+                                  const double* eta_offset, const double* row_weight,
+                                  const int64_t* offsets, int32_t K, int32_t p,
+                                  int32_t fit_intercept, const double* center,
+                                  const double* scale, const double* betas,
+                                  int64_t beta_part_stride, int32_t rows_per_chunk, double* gram,
+                                  double* score, double* gram_sum, double* score_sum,
+                                  void* stream) {
+  return gram_dense(family, kind, X, y, eta_offset, row_weight, offsets, K, p, fit_intercept,
+                    center, scale, betas, beta_part_stride, rows_per_chunk, gram, score, gram_sum,
+                    score_sum, stream);
+}
+
 int dlsa_glm_gof_categorical(int32_t family, const double* Xn, const uint8_t* codes,
                              const double* y, const double* eta_offset,
                              const double* row_weight, const int64_t* offsets, int32_t K,

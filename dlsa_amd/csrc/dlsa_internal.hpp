@@ -439,6 +439,25 @@ struct GofArgs : EvalArgsWgt {
   GofOut gof;
 };
 
+// Score outer-product pass (score_pass_impl.hpp): per partition the weighted
+// Gram sum_i d_i x_i x_i^T and the score sum_i s_i x_i at one coefficient
+// vector per partition (betas + k * beta_part_stride, stride 0 or P; nbeta is
+// 1 and `partial` unused).  Its kernels take this struct of their own; the
+// row extras are run-time nullable pointers.
+enum : int32_t { GRAM_SCORE = DLSA_GRAM_SCORE, GRAM_INFORMATION = DLSA_GRAM_INFORMATION };
+struct GramArgs : EvalArgsWgt {
+  int64_t beta_part_stride;
+  int32_t kind;    // GRAM_SCORE: d = s^2; GRAM_INFORMATION: d = omega w
+  double* slab_G;  // [n_chunks, T, 16, 16] partial lower-triangle tiles (the fit's slab layout)
+  double* slab_s;  // [n_chunks, 16 NT] partial scores
+};
+// (sets nslot and slot_bytes itself)
+hipError_t launch_score_pass(const GramArgs& a, int family, int n_chunks, hipStream_t s);
+// gram[k] (both triangles) and score[k]: the sums of partition k's chunk
+// partials in chunk order; then, where set, their sums over k ascending
+hipError_t launch_gram_reduce(const GramArgs& a, const int32_t* pcb, int K, double* gram,
+                              double* score, double* gram_sum, double* score_sum, hipStream_t s);
+
 // Wide-P path (DLSA_MAX_P_FUSED < P <= DLSA_MAX_P, wide_exact.hip): a row
 // pass (eta, weights, gradient, log-lik) and a separate Gram pass over
 // 128x128 output tiles of the padded PP = 128 * NB Hessian.

@@ -50,6 +50,22 @@ __device__ __forceinline__ LogisticLink logistic_link(double e) {
   return {ea, e >= 0.0 ? inv : ea * inv, ea * inv * inv};
 }
 
+// The mean and the variance function of a row at eta = e, for the passes that
+// take both as values (the score pass, score_pass_impl.hpp): the logistic
+// link above with the library division; mu = w = exp(e) for the Poisson
+// family.  The caller keeps a padded row's eta out (exp of it may overflow).
+struct RowMean { double mu, w; };
+template <int FAM>
+__device__ __forceinline__ RowMean row_mean(double e) {
+  if constexpr (FAM == FAMILY_POISSON) {
+    const double mu = exp(e);
+    return {mu, mu};
+  } else {
+    const LogisticLink k = logistic_link<RCP_DIV>(e);
+    return {k.mu, k.w};
+  }
+}
+
 // One row's term of the evaluation passes at eta = e; lg = lgamma(y + 1) is
 // computed once per row by the caller (0 for the logistic family); om the
 // prior weight (the constant 1 without one).

@@ -154,6 +154,124 @@ def gof_sharded(X, y, offsets, betas, fit_intercept=False, center=None, scale=No
     return {"deviance": tot[:B], "pearson": tot[B:2 * B], "n_pos": int(round(float(tot[-1])))}
 
 
+def combine_gram(gram_sum, score_sum, group=None):
+    """The exchange step of ``gram_sharded``: ONE ``combine`` of this rank's
+    ``[gram_sum | score_sum]`` (P^2 + P doubles; host or device tensors).
+    Returns numpy ``(gram_sum [P, P], score_sum [P])``, the same on every
+    rank."""
+    import torch
+
+    P = score_sum.numel()
+    tot = combine(torch.cat([gram_sum.reshape(-1), score_sum.reshape(-1)]), group).cpu().numpy()
+    return tot[:P * P].reshape(P, P).copy(), tot[P * P:].copy()
+
+
+def gram_sharded(X, y, offsets, thetas=None, beta=None, kind="score", family="logistic",
+                 eta_offset=None, exposure=None, sample_weight=None, fit_intercept=False,
+                 center=None, scale=None, rows_per_chunk=0, group=None):
+    """``loglik_sharded`` for the score outer-product pass
+    (``glm_gram_batched``, the same arguments; X, y, offsets describe the LOCAL
+    shard): the sum over every partition of the job of the meat (``kind`` =
+    "score") or the information matrix ("information") and of the score
+    vector.  ONE all-reduce of this rank's P^2 + P totals.  Returns a dict of
+    numpy arrays, the same on every rank: ``gram_sum`` [P, P], ``score_sum``
+    [P]."""
+    from .models import glm_gram_batched
+
+    g = glm_gram_batched(family, X, y, offsets, thetas=thetas, beta=beta, kind=kind,
+                         eta_offset=eta_offset, exposure=exposure, sample_weight=sample_weight,
+                         fit_intercept=fit_intercept, center=center, scale=scale,
+                         return_sum=True, rows_per_chunk=rows_per_chunk)
+    G, sc = combine_gram(g["gram_sum"], g["score_sum"], group)
+    return {"gram_sum": G, "score_sum": sc}
+
+
+def sandwich_cov(A, M):
+    """The sandwich (Huber-White) covariance of the combined estimate and the
+    information matrix it implies, from A = sum_k Sig_inv_k and the meat M =
+    sum_k M_k (both [P, P], symmetric):
+
+    * ``cov``  = A^-1 M A^-1, symmetrised -- Cov(theta~) for theta~ = A^-1
+      sum_k S_k theta_k with independent partitions, Cov(theta_k) = S_k^-1 M_k
+      S_k^-1 (the per-partition inverses cancel);
+    * ``info`` = A M^-1 A = cov^-1, what LARS / DBIC take in place of A.  With
+      M = phi A these are phi A^-1 and A / phi: the quasi-likelihood scaling.
+
+    Both come from the Cholesky factor of M and solves with A, never from
+    explicit inverses multiplied together.  A meat that is not positive
+    definite (fewer rows with a positive weight than P over the whole job)
+    raises ``ValueError``.  Returns ``(cov, info)``."""
+    A = np.asarray(A, dtype=np.float64)
+    M = np.asarray(M, dtype=np.float64)
+    if A.ndim != 2 or A.shape[0] != A.shape[1] or M.shape != A.shape:
+        raise ValueError("A and M must be square matrices of one shape")
+    P = A.shape[0]
+    M = 0.5 * (M + M.T)
+    bad = "the meat M is not positive definite (fewer rows with a positive weight than P?)"
+    if not np.all(np.isfinite(M)) or not np.all(np.isfinite(A)):
+        raise ValueError("A or M is not finite")
+    try:
+        L = np.linalg.cholesky(M)
+    except np.linalg.LinAlgError as e:
+        raise ValueError(bad) from e
+    # a rank-deficient M that rounding let through: a pivot at rounding level
+    if not np.min(np.diag(L)) ** 2 > P * np.finfo(np.float64).eps * np.max(np.diag(M)):
+        raise ValueError(bad)
+    Y = np.linalg.solve(A, M)        # A^-1 M
+    cov = np.linalg.solve(A, Y.T)    # A^-1 (A^-1 M)^T = A^-1 M A^-1 (A, M symmetric)
+    cov = 0.5 * (cov + cov.T)
+    Z = np.linalg.solve(L, A)        # L^-1 A;  info = Z^T Z = A L^-T L^-1 A
+    info = Z.T @ Z
+    return cov, 0.5 * (info + info.T)
+
+
+_COV_TYPES = (None, "model", "HC0", "HC1")
+
+
+def _cov_summary(out, cov, wlse):
+    """cov and what a coefficient table prints from it: std_err, z = wlse /
+    std_err and the two-sided normal p_value = erfc(|z| / sqrt 2)."""
+    import math
+
+    se = np.sqrt(np.diag(cov))
+    z = wlse / se
+    out["cov"] = cov
+    out["std_err"] = se
+    out["z"] = z
+    out["p_value"] = np.array([math.erfc(abs(float(v)) / math.sqrt(2.0)) for v in z])
+
+
+def _meat_sum(fit, X, y, offsets, family, eta_offset, exposure, sample_weight, fit_intercept,
+              center, scale, group):
+    """sum_k M_k over the partitions the combine counts (status ok or maxiter)
+    and over the ranks -- one score pass at each partition's own ``fit.theta``
+    row, the others zeroed before the sum, one all-reduce -- with, in the same
+    buffer, n+ (the rows with omega > 0 of those partitions; one more
+    goodness-of-fit pass only when weights are given) and their count K_ok.
+    Returns (M [P, P], n+, K_ok)."""
+    import torch
+
+    from .models import glm_gof_batched, glm_gram_batched
+
+    kw = dict(thetas=fit.theta, eta_offset=eta_offset, exposure=exposure,
+              sample_weight=sample_weight, fit_intercept=fit_intercept, center=center,
+              scale=scale)
+    g = glm_gram_batched(family, X, y, offsets, kind="score", **kw)
+    ok = fit.status <= 1
+    zero = torch.zeros((), dtype=torch.float64, device=ok.device)
+    M = torch.where(ok[:, None, None], g["gram"], zero).sum(0)
+    if sample_weight is not None:
+        rows = glm_gof_batched(family, X, y, offsets, **kw)["n_pos"].to(torch.float64)
+    else:
+        rows = torch.from_numpy(np.diff(np.asarray(offsets, dtype=np.int64)).astype(np.float64)
+                                ).to(ok.device)
+    npos = torch.where(ok, rows, zero).sum()
+    tot = combine(torch.cat([M.reshape(-1), torch.stack([npos, ok.sum().to(torch.float64)])]),
+                  group).cpu().numpy()
+    P = fit.P
+    return tot[:P * P].reshape(P, P).copy(), float(tot[-2]), float(tot[-1])
+
+
 def _pearson_dispersion(fit, X, y, offsets, codes, levels, family, eta_offset, exposure,
                         sample_weight, fit_intercept, center, scale, group):
     """phi = sum_k chi^2_k / (sum_k n+_k - K_ok P): the Pearson chi-square of
@@ -186,7 +304,8 @@ def _pearson_dispersion(fit, X, y, offsets, codes, levels, family, eta_offset, e
 
 def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
                      group=None, codes=None, levels=None, family="logistic", eta_offset=None,
-                     exposure=None, dispersion=None, sample_weight=None, **fit_kw):
+                     exposure=None, dispersion=None, cov_type=None, sample_weight=None,
+                     **fit_kw):
     """Fit this rank's partitions on its GPU and return the global DLSA result.
 
     X, y, offsets describe the LOCAL shard (rows already on this rank's
@@ -216,6 +335,32 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
     The WLSE is unchanged; LARS / DBIC see the scaled information matrix.  The
     result gains ``"dispersion"``.  Non-positive degrees of freedom raise
     ``ValueError``.
+    ``cov_type``: None (the default: exactly the call without the keyword, no
+    new keys), or the covariance of the WLSE the result gains as ``"cov"``
+    with ``"std_err"`` = sqrt(diag cov), ``"z"`` = wlse / std_err and
+    ``"p_value"`` = erfc(|z| / sqrt 2):
+
+    * "model": (sum_k Sig_inv_k)^-1, times phi with ``dispersion="pearson"``;
+      no new pass.  Right when Var(y) = phi V(mu).
+    * "HC0": the sandwich A^-1 (sum_k M_k) A^-1 (Huber-White; R's
+      ``sandwich::vcovHC(type="HC0")``), A = sum_k Sig_inv_k, M_k = sum_i s_i^2
+      x_i x_i^T with s_i = omega_i (y_i - mu_i(theta_k)): one score pass at
+      each partition's own ``fit.theta`` (``glm_gram_batched``), summed over
+      the partitions the combine counts, and one more all-reduce of P^2 + 2
+      doubles.  omega enters the meat squared, the precision / survey-weight
+      convention of R's ``sandwich::estfun``: frequency weights are not
+      replicated rows here.  The WLSE and ONESHOT are unchanged; LARS / DBIC
+      run on ``info`` = A M^-1 A in place of A (``sandwich_cov``; with M = phi
+      A today's S / phi).  The result also gains ``"meat_sum"`` (sum_k M_k)
+      and ``"info"``.
+    * "HC1": HC0 times n+ / (n+ - K_ok P), n+ the rows with omega > 0 of the
+      K_ok counted partitions (the degrees of freedom of ``dispersion=``; with
+      weights one more goodness-of-fit pass counts them).  A non-positive
+      denominator raises ``ValueError``.
+
+    "HC0" / "HC1" with ``dispersion="pearson"`` raise ``ValueError`` (the
+    sandwich already absorbs phi), and with ``codes=`` too: the score pass
+    covers the dense layout only.
     """
     from .models import (logistic_model_batched, logistic_model_batched_categorical,
                          logistic_model_batched_categorical_weighted,
@@ -229,6 +374,15 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
         raise ValueError("eta_offset / exposure need family='poisson'")
     if dispersion not in (None, "pearson"):
         raise ValueError(f"dispersion must be None or 'pearson', not {dispersion!r}")
+    if cov_type not in _COV_TYPES:
+        raise ValueError(f"cov_type must be None, 'model', 'HC0' or 'HC1', not {cov_type!r}")
+    robust = cov_type in ("HC0", "HC1")
+    if robust and dispersion is not None:
+        raise ValueError(f"cov_type={cov_type!r} with dispersion='pearson': the sandwich already "
+                         "absorbs the dispersion; give one of them")
+    if robust and codes is not None:
+        raise ValueError(f"cov_type={cov_type!r} with codes=: the score pass covers the dense "
+                         "layout only (the categorical-code layout is not supported yet)")
     if family == "poisson" and codes is not None:
         fit = poisson_model_batched_categorical(X, codes, y, offsets, levels,
                                                 sample_weight=sample_weight,
@@ -259,7 +413,24 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
     else:
         fit = logistic_model_batched(X, y, offsets, fit_intercept=fit_intercept, **fit_kw)
     buf = reduce_partitions_device(fit, n_rows=True)
-    if dispersion is None:
+    if robust:
+        M, npos, k_ok = _meat_sum(fit, X, y, offsets, family, eta_offset, exposure, sample_weight,
+                                  fit_intercept, fit_kw.get("center"), fit_kw.get("scale"), group)
+        b = combine(buf, group).cpu().numpy()
+        S, v, st, K = split_reduced(b[:-1], fit.P)
+        factor = 1.0
+        if cov_type == "HC1":
+            dof = npos - k_ok * fit.P
+            if not dof > 0:
+                raise ValueError(f"cov_type='HC1': residual degrees of freedom {dof:g} = rows "
+                                 "with a positive weight - fitted partitions x P is not positive")
+            factor = npos / dof
+        wlse = np.linalg.lstsq(S, v, rcond=None)[0]
+        cov, info = sandwich_cov(S, M * factor)
+        out = finish(info, info @ wlse, st, K, int(round(float(b[-1]))), fit_intercept, lars_type)
+        out.update(wlse=wlse, Sig_inv_sum=S, info=info, meat_sum=M)
+        _cov_summary(out, cov, wlse)
+    elif dispersion is None:
         out = combine_and_finish(buf, fit.P, fit_intercept, lars_type, group)
     else:
         phi = _pearson_dispersion(fit, X, y, offsets, codes, levels, family, eta_offset, exposure,
@@ -269,5 +440,9 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
         S, v, st, K = split_reduced(b[:-1], fit.P)
         out = finish(S / phi, v / phi, st, K, int(round(float(b[-1]))), fit_intercept, lars_type)
         out["dispersion"] = phi
+    if cov_type == "model":
+        S = out["Sig_inv_sum"]  # (with a dispersion S / phi: its inverse is phi S^-1)
+        cov = np.linalg.solve(S, np.eye(fit.P))
+        _cov_summary(out, 0.5 * (cov + cov.T), out["wlse"])
     out["fit"] = fit
     return out

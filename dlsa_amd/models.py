@@ -1028,6 +1028,71 @@ def glm_gof_batched_categorical(family, Xn, codes, y, offsets, levels, betas=Non
     return _gof_groups(call, betas, thetas, P, K, dev, return_sum)
 
 
+_GRAM_KINDS = {"score": _hip.GRAM_SCORE, "information": _hip.GRAM_INFORMATION}
+
+
+def glm_gram_batched(family, X, y, offsets, thetas=None, beta=None, kind="score",
+                     eta_offset=None, exposure=None, sample_weight=None, fit_intercept=False,
+                     center=None, scale=None, return_sum=False, rows_per_chunk=0, device=None):
+    """Score outer products of a GLM in one more pass over X (8 (p + 1) bytes
+    per row plus 8 per row extra; ``dlsa_glm_gram_batched``, fp64 MFMA): per
+    partition k at its coefficient vector, with s_i = omega_i (y_i - mu_i),
+
+    * ``gram`` [K, P, P] = sum_i d_i x_i x_i^T, exactly symmetric, and
+    * ``score`` [K, P] = sum_i s_i x_i (zero at a converged fit's own theta).
+
+    ``kind`` = "score": d = s^2, the meat M_k of the sandwich (Huber-White,
+    HC0) covariance; omega enters squared, the precision / survey-weight
+    convention of R's ``sandwich::estfun`` -- frequency weights are not
+    replicated rows here.  ``kind`` = "information": d = omega w (w = mu (1 -
+    mu) or mu), the information matrix, a fit's ``sig_inv``, at any beta.
+
+    Exactly one of ``thetas`` [K, P] (partition k at its own row) and ``beta``
+    [P] (every partition at the same vector, e.g. the WLSE).  ``family``:
+    "logistic" or "poisson"; ``eta_offset`` / ``exposure`` (Poisson only) and
+    ``sample_weight`` as in the fits, with their ``ValueError`` cases; P =
+    p + intercept <= 192 (a wider one raises ``DlsaHipError``).  ``rows_per_chunk``: 0 (automatic) or the rows one
+    workgroup sums; the sums' last bits depend on it.
+
+    Returns a dict of device tensors ``gram``, ``score``; with ``return_sum``
+    also ``gram_sum`` [P, P] and ``score_sum`` [P], the sums over k ascending.
+    Fixed summation order: two calls give the same bits."""
+    if kind not in _GRAM_KINDS:
+        raise ValueError(f"kind must be 'score' or 'information', not {kind!r}")
+    if (beta is None) == (thetas is None):
+        raise ValueError("give exactly one of thetas [K, P] (each partition at its own row) and "
+                         "beta [P] (every partition at the same vector)")
+    fam = _check_gof_args(family, X, beta, thetas, eta_offset, exposure, sample_weight)
+    if int(rows_per_chunk) < 0:
+        raise ValueError("rows_per_chunk must be >= 0")
+    p = _shape(X)[1]
+    P = p + (1 if fit_intercept else 0)
+    K = _size(offsets) - 1
+    coef = thetas if beta is None else beta
+    if beta is not None and _size(coef) != P:
+        raise ValueError("beta must be [P]: one coefficient vector for every partition")
+    if thetas is not None and (_size(coef) != K * P or
+                               (len(_shape(coef)) == 2 and _shape(coef) != (K, P))):
+        raise ValueError("thetas must be [K, P]: one row per partition")
+    dev, Xd, yd, offs, cd, sd = _dense_inputs(X, y, offsets, center, scale, device)
+    od, wd = _gof_extras(family, eta_offset, exposure, sample_weight, dev)
+    bd = _dev_f64(coef, dev).reshape(-1)
+    f64 = dict(dtype=torch.float64, device=dev)
+    gram, score = torch.empty((K, P, P), **f64), torch.empty((K, P), **f64)
+    gsum = torch.empty((P, P), **f64) if return_sum else None
+    ssum = torch.empty((P,), **f64) if return_sum else None
+    rc = _hip.load().dlsa_glm_gram_batched_chunked(
+        fam, _GRAM_KINDS[kind], _ptr(Xd), _ptr(yd), _ptr(od), _ptr(wd),
+        offs.ctypes.data_as(ctypes.c_void_p), K, p, int(bool(fit_intercept)), _ptr(cd), _ptr(sd),
+        _ptr(bd), P if thetas is not None else 0, int(rows_per_chunk), _ptr(gram), _ptr(score),
+        _ptr(gsum), _ptr(ssum), _stream(dev))
+    _hip.check(rc, "dlsa_glm_gram_batched")
+    out = {"gram": gram, "score": score}
+    if return_sum:
+        out.update(gram_sum=gsum, score_sum=ssum)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # reference-signature wrapper (one Spark group)
 # ---------------------------------------------------------------------------

@@ -107,6 +107,9 @@ extern "C" {
 /* Candidates of one goodness-of-fit pass: the most at which none of its
    kernels spills (two sums per candidate). */
 #define DLSA_MAX_GOF_CANDIDATES 16
+/* The row weight d_i of dlsa_glm_gram_batched's sum_i d_i x_i x_i^T. */
+#define DLSA_GRAM_SCORE 0        /* d = s^2, s = omega (y - mu): the sandwich's meat */
+#define DLSA_GRAM_INFORMATION 1  /* d = omega w: the information matrix at beta */
 
 typedef struct dlsa_fit_options {
   int32_t hessian_mode;     /* DLSA_HESSIAN_MIXED (default) or _FP64 */
@@ -666,6 +669,52 @@ int dlsa_glm_gof_batched(int32_t family, const double* X, const double* y,
                          const double* center, const double* scale, const double* betas,
                          int32_t n_beta, int64_t beta_part_stride, double* deviance,
                          double* pearson, double* n_pos, double* sums, void* stream);
+
+/*
+ * Score outer products: one more pass over the dense layout (8 (p + 1) bytes
+ * per row plus 8 per row extra, each streamed once) that gives, per partition
+ * k at its coefficient vector beta_k, with eta_i = x_i . beta_k (+
+ * eta_offset_i), mu_i the family's mean, omega_i the prior weight and
+ * s_i = omega_i (y_i - mu_i):
+ *   gram[k]  = sum_i d_i x_i x_i^T   [K, P, P], both triangles, exactly symmetric
+ *   score[k] = sum_i s_i x_i         [K, P]
+ *   kind DLSA_GRAM_SCORE:        d_i = s_i^2 -- the meat M_k of the sandwich
+ *       (Huber-White, HC0) covariance A^-1 (sum_k M_k) A^-1; omega enters
+ *       squared: precision / survey weights, not replicated rows
+ *   kind DLSA_GRAM_INFORMATION:  d_i = omega_i w_i, w = mu (1 - mu) (logistic)
+ *       or mu (Poisson) -- the information matrix (a fit's Sig_inv) at beta_k.
+ * x_i is the standardised row ((x - center) / scale when both are given) with
+ * the implicit intercept column first when fit_intercept is set.
+ * family: DLSA_FAMILY_LOGISTIC or DLSA_FAMILY_POISSON, any other
+ * DLSA_E_UNSUPPORTED; any other kind DLSA_E_INVALID.  eta_offset, row_weight:
+ * [n_total] fp64, device, or NULL; an offset with the logistic family is
+ * DLSA_E_INVALID.  Neither is checked here.
+ * betas, beta_part_stride: partition k is evaluated at betas + k *
+ * beta_part_stride -- 0: one [P] vector for every partition; P: betas is
+ * [K, P], each partition at its own row.  Any other stride is DLSA_E_INVALID.
+ * Limit: P = p + fit_intercept <= DLSA_MAX_P_FUSED (192), else
+ * DLSA_E_UNSUPPORTED before any launch.  An empty partition gets zero blocks.
+ * gram_sum [P, P], score_sum [P]: NULL, or the sums over k ascending.  The
+ * chunk partials go to a stream-ordered scratch and are summed in chunk
+ * order: two calls give the same bits.  fp64 throughout (v_mfma_f64_16x16x4).
+ */
+int dlsa_glm_gram_batched(int32_t family, int32_t kind, const double* X, const double* y,
+                          const double* eta_offset, const double* row_weight,
+                          const int64_t* offsets, int32_t K, int32_t p, int32_t fit_intercept,
+                          const double* center, const double* scale, const double* betas,
+                          int64_t beta_part_stride, double* gram, double* score,
+                          double* gram_sum, double* score_sum, void* stream);
+/* ... with the rows of a chunk (one workgroup's share of a partition) chosen
+ * by the caller; rows_per_chunk = 0: automatic, as above.  The sums are taken
+ * in chunk order, so their last bits depend on it. */
+int dlsa_glm_gram_batched_chunked(int32_t family, int32_t kind, const double* X, const double* y,
+                                  const double* eta_offset, const double* row_weight,
+                                  const int64_t* offsets, int32_t K, int32_t p,
+                                  int32_t fit_intercept, const double* center,
+                                  const double* scale, const double* betas,
+                                  int64_t beta_part_stride, int32_t rows_per_chunk, double* gram,
+                                  double* score, double* gram_sum, double* score_sum,
+                                  void* stream);
 
 /*
  * dlsa_glm_gof_batched on the categorical-code layout of
