@@ -736,7 +736,10 @@ hipError_t launch_ols_stream(const PassArgs& a, int NT, bool standardize, int n_
                              hipStream_t s);
 hipError_t launch_irls_coop(const PassArgsWgt& a, int NT, int prec, bool standardize, int family,
                             int n_chunks, hipStream_t s);
-int coop_slot_bytes(int NT, int p, int n_extras = 0);  // + 256 B per row extra behind y
+// the ring slot of a launch over X (coop_slot, irls_coop_impl.hpp: a KiB less
+// where every block starts 16-byte aligned and p % 4 == 0); + 256 B per row
+// extra behind y
+int coop_slot_bytes(int NT, const double* X, int p, int n_extras = 0);
 int coop_extra_bytes(int NT);  // LDS beyond the ring
 hipError_t launch_newton_solve(const SolveArgs& a, int K, hipStream_t s);
 hipError_t launch_fit_init(const int64_t* offsets_dev, int K, int P, int start_phase,

@@ -89,7 +89,7 @@ void FusedFit::set_pass_args(const Plan& pl, const Workspace& ws, const Layout& 
   // row phase and barrier waits overlap the other's tile phase (measured
   // 27.4 -> 21.8 ms per bf16 pass at config 2 against one workgroup with a
   // deeper ring)
-  pa.slot_bytes = coop_slot_bytes(pl.NT, f.p, ex_count(pass_extras(pa)));
+  pa.slot_bytes = coop_slot_bytes(pl.NT, pa.X, f.p, ex_count(pass_extras(pa)));
   const int wg_per_cu = pl.NT < 8 ? 2 : 1;
   const int budget = 160 * 1024 / wg_per_cu - coop_extra_bytes(pl.NT);
   pa.nslot = std::max(2, std::min(budget / pa.slot_bytes, 6));

@@ -33,8 +33,8 @@ namespace dlsa {
 DLSA_COOP_UNITS(DLSA_DECLARE)
 static const UnitRow<CoopUnitFn> kCoopUnits[] = {DLSA_COOP_UNITS(DLSA_ROW)};
 
-int coop_slot_bytes(int NT, int p, int n_extras) {
-  return coop_slot_bytes_impl(NT, p, n_extras);
+int coop_slot_bytes(int NT, const double* X, int p, int n_extras) {
+  return coop_slot(NT, p, n_extras, coop_x_aligned(X, p)).bytes;
 }
 int coop_extra_bytes(int NT) { return coop_extra_bytes_impl(NT); }
 

@@ -79,8 +79,7 @@ struct CG {
                                                // (24 dwords) makes the ds_read_b128 operand
                                                // reads (lane groups of MI355X_MICROARCH.md
                                                // "LDS") conflict-free -- 80 B is 2-way
-  static constexpr int MAX_PIECES = (RB * PMAX * 8 + 16 + 1023) / 1024;
-  static constexpr int MAX_D = (MAX_PIECES + W - 1) / W;  // DMA pieces per wave per block
+  static constexpr int MAX_PIECES = (RB * PMAX * 8 + 8 + 1023) / 1024;  // coop_slot, unaligned
   // tiles of wave `wid`: t in [wid*TPW, min(T, (wid+1)*TPW))
   static constexpr unsigned col_mask(int wid) {
     unsigned m = 0;
@@ -95,23 +94,48 @@ struct CG {
   }
 };
 
-__host__ __device__ __forceinline__ int npieces_for(int p) { return (RB * p * 8 + 16 + 1023) / 1024; }
-
 }  // namespace
 
 // Waves per workgroup: 4 for P <= 128 (8 lanes per row in the row phase),
 // 8 above (16 lanes per row keeps the per-lane feature count <= 12).
 constexpr int coop_waves(int NT) { return NT > 8 ? 8 : 4; }
 
-// A slot holds exactly the block's pieces: a wave's surplus issues (the piece
-// count is rounded up to the wave count so that every wave waits on the same
-// vmcnt) re-load the last piece onto itself.
-// Behind them, PMAX doubles of pad and the row streams: y and the row extras
-// (glm_row.hpp).  (constexpr for coop_ring_fits below, so npieces_for(p) is
-// spelled out)
+// The ring slot of one 32-row block, the one definition the kernel, the host's
+// slot size (coop_slot_bytes) and the ring depth (set_pass_args) share:
+//   [PAD 16 B][npieces KiB pieces of X][PMAX doubles of pad][y][row extras]
+// A block's rows are RB p 8 bytes from `start`, DMA'd from start & ~15 on, so
+// the pieces cover span = RB p 8 + s bytes, s the largest start & 15 a block of
+// the launch can have: 0 when p is even and X is 16-byte aligned (every block
+// then starts on a 16-byte boundary), 8 otherwise.  With p % 4 == 0 and s = 0
+// the span is a whole number of KiB and no piece reaches into the next block
+// (which, streamed non-temporally, would fetch that KiB from HBM twice).
+// The pad: the lanes of the padded features f >= P of the block's last row
+// read up to PMAX doubles behind the block.  Where the last piece ends with
+// the block no DMA ever writes those bytes, and nothing else does but the last
+// block's zeroing: they stay the zeros of the ring's initial clear (they are
+// multiplied by beta = 0 / w = 0 only, but must be finite).
+// Behind the pad the row streams: y and the row extras (glm_row.hpp).
 static_assert(RB == kRowStreamRows, "a block's rows are one row stream of the slot");
-constexpr int coop_slot_bytes_impl(int NT, int p, int n_extras = 0) {
-  return 16 + ((RB * p * 8 + 16 + 1023) / 1024) * 1024 + 16 * NT * 8 + row_streams_bytes(n_extras);
+struct CoopSlot {
+  int npieces;  // KiB pieces of X per block
+  int rows_off;  // byte offset of y (the row extras follow)
+  int bytes;
+};
+constexpr CoopSlot coop_slot(int NT, int p, int n_extras, bool aligned) {
+  const int np = (RB * p * 8 + (aligned ? 0 : 8) + 1023) / 1024;
+  const int rows_off = 16 + np * 1024 + 16 * NT * 8;
+  return CoopSlot{np, rows_off, rows_off + row_streams_bytes(n_extras)};
+}
+// Whether every block of a launch over X starts on a 16-byte boundary: decided
+// from the X pointer of the fit, by the host (set_pass_args) and by the kernel
+// (from PassArgs::X) alike.
+__host__ __device__ __forceinline__ bool coop_x_aligned(const double* X, int p) {
+  return (p & 1) == 0 && ((uintptr_t)X & 15) == 0;
+}
+// DMA loads per block of the wave with the most: the pieces, y and the row
+// extras dealt round robin over the W waves, each issued once
+constexpr int coop_max_loads(int NT, int W, int nld) {
+  return (coop_slot(NT, 16 * NT, 0, false).npieces + nld + W - 1) / W;
 }
 
 // LDS beyond the ring: w, r of the block [2][RB] fp64, center / 1/scale
@@ -122,12 +146,12 @@ constexpr int coop_extra_bytes_impl(int NT) {
   return (2 * RB + 2 * 16 * NT) * 8 + 16 * NT * (RB + 16) * 2;
 }
 
-// The smallest ring (nslot = 2) of the widest slot of every NT, with both row
-// extras, fits the LDS share of a workgroup (set_pass_args, fit_fused.hip:
+// The smallest ring (nslot = 2) of the widest slot of every NT (unaligned), with
+// both row extras, fits the LDS share of a workgroup (set_pass_args, fit_fused.hip:
 // two workgroups per CU below NT = 8).
 constexpr bool coop_ring_fits(int n_extras) {
   for (int NT = 1; NT <= 12; ++NT)
-    if (2 * coop_slot_bytes_impl(NT, 16 * NT, n_extras) + coop_extra_bytes_impl(NT) >
+    if (2 * coop_slot(NT, 16 * NT, n_extras, false).bytes + coop_extra_bytes_impl(NT) >
         160 * 1024 / (NT < 8 ? 2 : 1))
       return false;
   return true;
@@ -206,8 +230,8 @@ __device__ __forceinline__ void store_tiles(Acc (&acc)[(CG<NT, W>::TPW)], double
 // value of the bf16 image) into a.zcolmax (2: the bf16 passes of partitions
 // near convergence); the Ozaki exact pass takes its digit scales from the
 // last records (irls_oz_impl.hpp)
-// EX (row extras, EX_* mask): each streams like y, one more load per wave and
-// block behind y (RowStreams, glm_row.hpp).
+// EX (row extras, EX_* mask): each streams like y, one more load per block,
+// placed behind y (RowStreams, glm_row.hpp).
 //   EX_OFS (FAMILY_POISSON only): eta = x . theta + a.eta_offset[row]
 //   EX_WGT: prior weights omega = a.row_weight[row]: w, r and the row's
 //   log-likelihood terms are multiplied by omega once, after mu (so the bf16 /
@@ -223,10 +247,12 @@ void irls_coop_kernel(const typename pass_args_of<EX>::type a) {
   static_assert(!RS::OFS || FAM == FAMILY_POISSON, "the offset is the Poisson family's");
   static_assert(!RS::WGT || CM == 0, "no digit-scale records of a weighted pass");
   constexpr int NLD = RS::NLD;                // loads per block beside X: y and the row extras
-  constexpr int MAXW = 4 * (G::MAX_D + NLD);  // nslot <= 6
-  // a wave has at most nslot - 1 <= 5 blocks of d + NLD <= MAX_D + NLD loads
-  // outstanding: within the 6-bit vmcnt (5 (9 + 3) = 60 at NT = 8 with both extras)
-  static_assert(5 * (G::MAX_D + NLD) <= 63, "outstanding loads exceed the vmcnt counter");
+  static_assert(NLD <= W, "at most one row stream per wave");
+  constexpr int MAXL = coop_max_loads(NT, W, NLD);  // a wave's loads per block, at most
+  constexpr int MAXW = 4 * MAXL;                    // nslot <= 6
+  // a wave has at most nslot - 1 <= 5 blocks of its <= MAXL loads outstanding:
+  // within the 6-bit vmcnt (5 x 9 = 45 at NT = 8, 33 + 3 items over 4 waves)
+  static_assert(5 * MAXL <= 63, "outstanding loads exceed the vmcnt counter");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int chunk = blockIdx.x;
@@ -241,10 +267,11 @@ void irls_coop_kernel(const typename pass_args_of<EX>::type a) {
   const int nrows = __builtin_amdgcn_readfirstlane(a.chunk_rows[chunk]);
   const int nb = (nrows + RB - 1) / RB;
   const int nslot = a.nslot;
-  const int slot_bytes = a.slot_bytes;
-  const int npieces = npieces_for(p);
-  const int d = (npieces + W - 1) / W;
-  const int slot_x = G::PAD + npieces * 1024 + G::PMAX * 8;  // y follows (then the offset)
+  const CoopSlot sg = coop_slot(NT, p, ex_count(EX), coop_x_aligned(a.X, p));
+  const int slot_bytes = sg.bytes;  // == a.slot_bytes (launch_c)
+  const int npieces = sg.npieces;
+  const int slot_x = sg.rows_off;  // y (then the row extras)
+  static_assert(G::PAD == 16, "coop_slot's pad");
   double* wr = (double*)(smem + nslot * slot_bytes);       // [2][RB]: w, r of the block
   double* stdv = wr + 2 * RB;  // [2][PMAX]: center, 1/scale by feature (STD only)
   __bf16* obx = (__bf16*)(stdv + 2 * G::PMAX);  // [2][PMAX][OBS] bf16 operands (PREC_BF16)
@@ -320,46 +347,54 @@ void irls_coop_kernel(const typename pass_args_of<EX>::type a) {
   const uintptr_t xcb = (uintptr_t)(a.X + row0 * p) & ~(uintptr_t)15;
   const uintptr_t xend = a.x_last16 + 16;
   const __amdgpu_buffer_rsrc_t xr_rsrc = uniform_rsrc(xcb, xend - xcb);
-  const uintptr_t ycb = (uintptr_t)(a.y + row0);
-  const __amdgpu_buffer_rsrc_t yr_rsrc = uniform_rsrc(ycb, a.y_last4 + 4 - ycb);
   const int vx = lane * 16, vy = lane * 4;
-  [[maybe_unused]] __amdgpu_buffer_rsrc_t or_rsrc;
+  // The block's loads are npieces + NLD items -- the X pieces, then y and the
+  // row extras -- and wave wid issues items wid, wid + W, ...: each once.  So a
+  // wave has nx pieces and at most one row stream (NLD <= W); which one, its
+  // resource and its place in the slot are wave-uniform and fixed here, and
+  // the block loop runs two counted loops without a branch per item.
+  const int nx = __builtin_amdgcn_readfirstlane(wid < npieces ? (npieces - wid + W - 1) / W : 0);
+  const int rs = __builtin_amdgcn_readfirstlane((wid + W - npieces % W) % W);  // item npieces + rs
+  const int nrs = rs < NLD ? 1 : 0;
+  uintptr_t rcb = (uintptr_t)(a.y + row0), rend = a.y_last4 + 4;
+  int rs_off = slot_x;
   if constexpr (RS::OFS) {
-    const uintptr_t ocb = (uintptr_t)(a.eta_offset + row0);
-    or_rsrc = uniform_rsrc(ocb, a.o_last4 + 4 - ocb);
+    if (rs == 1) {
+      rcb = (uintptr_t)(a.eta_offset + row0);
+      rend = a.o_last4 + 4;
+      rs_off = slot_x + RS::OFS_OFF;
+    }
   }
-  [[maybe_unused]] __amdgpu_buffer_rsrc_t wr_rsrc;
   if constexpr (RS::WGT) {
-    const uintptr_t wcb = (uintptr_t)(a.row_weight + row0);
-    wr_rsrc = uniform_rsrc(wcb, a.w_last4 + 4 - wcb);
+    if (rs == (RS::OFS ? 2 : 1)) {
+      rcb = (uintptr_t)(a.row_weight + row0);
+      rend = a.w_last4 + 4;
+      rs_off = slot_x + RS::WGT_OFF;
+    }
   }
+  const __amdgpu_buffer_rsrc_t rs_rsrc = uniform_rsrc(rcb, rend - rcb);
   auto issue = [&](int blk) {
     const int bb = blk < nb ? blk : nb - 1;  // tail: harmless re-fetch, fixed counts
     char* sbase = smem + (blk % nslot) * slot_bytes;
     const uintptr_t start = (uintptr_t)(a.X + (row0 + (int64_t)bb * RB) * p);
     const int so = __builtin_amdgcn_readfirstlane((int)((start & ~(uintptr_t)15) - xcb));
-    for (int i = 0; i < d; ++i) {
-      int j = wid + W * i;
-      const int jj = j < npieces ? j : npieces - 1;
+    for (int i = 0; i < nx; ++i) {
+      const int j = wid + W * i;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          xr_rsrc, (lds_void_t*)(sbase + G::PAD + jj * 1024), 16, vx, so + jj * 1024, 0,
+          xr_rsrc, (lds_void_t*)(sbase + G::PAD + j * 1024), 16, vx, so + j * 1024, 0,
           (PREC == PREC_BF16 && NT == 7) ? DLSA_COOP_NT7_DMA_AUX : DLSA_X_DMA_AUX);
     }
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(yr_rsrc, (lds_void_t*)(sbase + slot_x), 4, vy,
-                                             bb * RB * 8, 0, 0);
-    if constexpr (RS::OFS)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          or_rsrc, (lds_void_t*)(sbase + slot_x + RS::OFS_OFF), 4, vy, bb * RB * 8, 0, 0);
-    if constexpr (RS::WGT)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          wr_rsrc, (lds_void_t*)(sbase + slot_x + RS::WGT_OFF), 4, vy, bb * RB * 8, 0, 0);
+    for (int i = 0; i < nrs; ++i)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_rsrc, (lds_void_t*)(sbase + rs_off), 4, vy,
+                                               bb * RB * 8, 0, 0);
   };
 
-  // every wave issues d + NLD loads per block, in block order: with at most
+  // a wave issues its nx + nrs loads per block, in block order: with at most
   // that many per block in flight for the nslot - 2 blocks after b, every
-  // load of block b (and before) has landed
+  // load of block b (and before) has landed.  vmcnt counts per wave, so the
+  // waves' counts need not be equal
   for (int b = 0; b < nslot - 1; ++b) issue(b);
-  const int keep = (nslot - 2) * (d + NLD);
+  const int keep = (nslot - 2) * (nx + nrs);
 
   for (int b = 0; b < nb; ++b) {
     wait_vmcnt_le<MAXW>(keep);  // this wave's pieces of block b landed
@@ -602,6 +637,9 @@ template <int NT, int W, int PREC, bool STD, int FAM, int CM = 0, int EX = EX_NO
 static hipError_t launch_c(const typename pass_args_of<EX>::type& a, int n_chunks,
                            hipStream_t s) {
   auto kern = irls_coop_kernel<NT, W, PREC, STD, FAM, CM, EX>;
+  // the kernel lays its ring out by coop_slot from the same X and p
+  if (a.slot_bytes != coop_slot(NT, a.p, ex_count(EX), coop_x_aligned(a.X, a.p)).bytes)
+    return hipErrorInvalidValue;
   const size_t lds =
       (size_t)a.nslot * a.slot_bytes + coop_extra_bytes_impl(NT);
   hipError_t e = ensure_max_lds((const void*)kern, 160 * 1024);

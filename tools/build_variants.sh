@@ -30,6 +30,7 @@ for v in "$@"; do
     dma0) D=DLSA_X_DMA_AUX=0 ;;
     sc1) D=DLSA_X_DMA_AUX=1 ;;
     coopdma0) D=DLSA_COOP_NT7_DMA_AUX=0 ;;  # the NT = 7 bf16 cooperative pass at the default policy
+    coopnt) D=DLSA_X_DMA_AUX=2 ;;  # every NT of the logistic / OLS cooperative pass non-temporal
     *) echo "unknown variant $v"; exit 1 ;;
   esac
   ONLY=None
@@ -42,7 +43,7 @@ for v in "$@"; do
     wn*) ONLY='["wide_newton.hip"]' ;;
     fab1) ONLY='["wide_fused.hip"]' ;;
     knobs) ONLY="[$HOST]" ;;
-    cmabl|coopdma0) ONLY='["irls_coop_g1.hip", "irls_coop_g2.hip", "irls_coop_g3.hip", "irls_coop_g4.hip", "irls_coop_g5.hip", "irls_coop_g6.hip"]' ;;
+    cmabl|coopdma0|coopnt) ONLY='["irls_coop_g1.hip", "irls_coop_g2.hip", "irls_coop_g3.hip", "irls_coop_g4.hip", "irls_coop_g5.hip", "irls_coop_g6.hip"]' ;;
   esac
   python -c "from dlsa_amd.build import build; print(build(force=True, out='var/libdlsa_hip_$v.so', defines='$D'.replace('-D', '').split(), only=$ONLY))"
 done
