@@ -92,19 +92,34 @@ __device__ __forceinline__ double row_gof_const(double yv) {
   else
     return (yv == 0.0 ? 0.0 : yv * log(yv)) + (yv == 1.0 ? 0.0 : (1.0 - yv) * log1p(-yv));
 }
-// Poisson: d = 2 omega (y (log y - eta) - (y - mu)), chi = omega (y - mu)^2 / mu.
+// Poisson: d = 2 omega (y (log y - eta) - (y - mu)), chi = omega (y - mu)^2 / mu,
+// formed as r (r / mu) with r = y - mu: r^2 alone overflows from eta = 355.
 // Logistic: d = 2 omega (rc - (y eta - softplus(eta))), and with ea = exp(-|eta|)
-// (y - mu)^2 / (mu (1 - mu)) = (y (1 + ea) - [eta >= 0 ? 1 : ea])^2 / ea: 1 - mu
-// is never formed.
+// (y - mu)^2 / (mu (1 - mu)) = t^2 / ea, t = a + b ea, (a, b) = (y - 1, y) at
+// eta >= 0 and (y, y - 1) below: 1 - mu is never formed.
+//
+// At saturation chi takes its limit, never 0 / 0 or inf / inf.  Logistic: a
+// matched row (a = 0: y = 1 at eta >= 0, y = 0 below, so b = +-1) has t = +-ea
+// and t / ea = +-1 exactly: chi = omega ea, without the cancellation of y (1 +
+// ea) - 1 (digits lost from |eta| = 16, all of them from 37 on); once ea has
+// underflowed to 0 (|eta| > 745.13) t = 0, which is selected to chi = 0 (and is
+// 0 as well where a grouped y equals mu).  Any other row is t (t / ea), +inf
+// once ea = 0; t^2 itself would underflow from |eta| = 373.  Poisson: y = 0 is
+// omega mu (0 once mu has underflowed), mu = +inf (eta > 709.78) is +inf, y > 0
+// over an underflowed mu is +inf.  The deviance needs no such care: its terms
+// are sums, and it is +inf where mu is.
 template <int FAM>
 __device__ __forceinline__ RowGof row_gof(double e, double yv, double om, double rc) {
   if constexpr (FAM == FAMILY_POISSON) {
     const double mu = exp(e), r = yv - mu;
-    return {2.0 * om * (yv * (rc - e) - r), om * (r * r / mu)};
+    const double chi = (yv == 0.0 || mu == HUGE_VAL) ? mu : r * (r / mu);
+    return {2.0 * om * (yv * (rc - e) - r), om * chi};
   } else {
     const double ea = exp(-fabs(e));
-    const double t = yv * (1.0 + ea) - (e >= 0.0 ? 1.0 : ea);
-    return {2.0 * om * (rc - (yv * e - (fmax(e, 0.0) + log1p(ea)))), om * (t * t / ea)};
+    const double a = e >= 0.0 ? yv - 1.0 : yv, b = e >= 0.0 ? yv : yv - 1.0;
+    const double t = fma(b, ea, a);
+    const double chi = t == 0.0 ? 0.0 : t * (t / ea);
+    return {2.0 * om * (rc - (yv * e - (fmax(e, 0.0) + log1p(ea)))), om * chi};
   }
 }
 

@@ -970,6 +970,16 @@ def glm_gof_batched(family, X, y, offsets, betas=None, thetas=None, eta_offset=N
     given in [0, 1], so grouped rows y = s / m with weight m work; it is not
     checked, and outside [0, 1] the sums are NaN.
 
+    At saturated linear predictors every row term takes its limit instead of
+    0 / 0: a logistic row on its own side (y = 1 at eta >= 0, y = 0 below) has
+    the Pearson term omega exp(-|eta|), 0 once that has underflowed (|eta| >
+    745.13), so a separated or steep fit keeps a finite ``pearson`` and
+    dispersion; a row on the wrong side grows like exp(|eta|) and is +inf from
+    there.  Poisson: y = 0 gives omega mu (0 for a dead row, e.g. an offset of
+    -800), y > 0 over an underflowed mu +inf, and an overflowed mu (eta >
+    709.78) +inf in both sums.  With y in [0, 1] (y >= 0) and positive weights
+    no sum is NaN.
+
     Returns a dict of device tensors: ``deviance`` [K, B], ``pearson`` [K, B]
     (fp64), ``n_pos`` [K] (int64); with ``return_sum`` also their sums over the
     partitions, ``deviance_sum`` [B], ``pearson_sum`` [B], ``n_pos_sum``.

@@ -652,6 +652,14 @@ int dlsa_poisson_loglik_categorical(const double* Xn, const uint8_t* codes, cons
  *             chi = omega (y - mu)^2 / (mu (1 - mu));
  *             y is taken as given in [0, 1] (a grouped row: y = s / m, omega =
  *             m) and not checked: outside it the sums are NaN.
+ *   At a saturated eta each term takes its limit; for y in [0, 1] (logistic)
+ *   and y >= 0 (Poisson) with omega > 0 no term is NaN.  Logistic, ea =
+ *   exp(-|eta|): a row on its own side (y = 1 at eta >= 0, y = 0 below) has
+ *   chi = omega ea, which is 0 once ea has underflowed (|eta| > 745.13); any
+ *   other row's chi grows like 1 / ea and is +inf from there.  Poisson: at
+ *   y = 0 chi = omega mu (0 once mu has underflowed, eta < -745.13), at y > 0
+ *   over such a mu chi = +inf; from eta > 709.78, where mu overflows, chi and d
+ *   are +inf.  (omega = 0 times such an infinity is NaN.)
  * eta_offset, row_weight: [n_total] fp64, device, or NULL; an offset with the
  * logistic family is DLSA_E_INVALID.  Neither is checked here.
  * betas, beta_part_stride: partition k is evaluated at the [n_beta, P] matrix
