@@ -173,6 +173,17 @@ SIGNATURES = {
         ctypes.c_int,
         [_I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _I32, _P, _P, _P, _P,
          _P]),
+    # row diagnostics: family; eta_offset and row_weight after y; betas and its stride,
+    # rfac and its stride; eta, mu, dev_res, pearson_res, leverage (the chunked entry:
+    # rows_per_chunk after rfac's stride)
+    "dlsa_glm_rows_batched": (
+        ctypes.c_int,
+        [_I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P,
+         _P, _P]),
+    "dlsa_glm_rows_batched_chunked": (
+        ctypes.c_int,
+        [_I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P, _I64, _I32, _P, _P, _P,
+         _P, _P, _P]),
     "dlsa_partition_rows": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "dlsa_last_fit_stats": (ctypes.c_int, [ctypes.POINTER(FitStats)]),
     "dlsa_reduce_partitions": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P]),

@@ -722,6 +722,124 @@ int dlsa_glm_gram_batched_chunked(int32_t family, int32_t kind, const double* X,
                     score_sum, stream);
 }
 
+static int rows_dense(int32_t family, const double* X, const double* y, const double* eta_offset,
+                      const double* row_weight, const int64_t* offsets, int32_t K, int32_t p,
+                      int32_t fit_intercept, const double* center, const double* scale,
+                      const double* betas, int64_t beta_part_stride, const double* rfac,
+                      int64_t rfac_part_stride, int32_t rows_per_chunk, double* eta, double* mu,
+                      double* dev_res, double* pearson_res, double* leverage, void* stream_) {
+  g_last_error.clear();
+  hipStream_t stream = (hipStream_t)stream_;
+  int rc = check_offsets(offsets, K);
+  if (rc != DLSA_OK) return rc;
+  if (family != FAMILY_LOGISTIC && family != FAMILY_POISSON) {
+    set_error("dlsa_glm_rows_batched: family must be DLSA_FAMILY_LOGISTIC or DLSA_FAMILY_POISSON");
+    return DLSA_E_UNSUPPORTED;
+  }
+  const int P = p + (fit_intercept ? 1 : 0);
+  if (p < 0 || P < 1 || rows_per_chunk < 0 || !betas ||
+      (center == nullptr) != (scale == nullptr)) {
+    set_error("dlsa_glm_rows_batched: invalid arguments (P >= 1, rows_per_chunk >= 0, center "
+              "and scale both or neither)");
+    return DLSA_E_INVALID;
+  }
+  if (P > DLSA_MAX_P_FUSED) {  // before any launch
+    set_error("dlsa_glm_rows_batched: P = p + intercept > DLSA_MAX_P_FUSED = " +
+              std::to_string(DLSA_MAX_P_FUSED) + " is not supported");
+    return DLSA_E_UNSUPPORTED;
+  }
+  if (eta_offset && family != FAMILY_POISSON) {
+    set_error("eta_offset is the Poisson family's");
+    return DLSA_E_INVALID;
+  }
+  if (beta_part_stride != 0 && beta_part_stride != P) {
+    set_error("dlsa_glm_rows_batched: beta_part_stride must be 0 or P");
+    return DLSA_E_INVALID;
+  }
+  if (rfac_part_stride != 0 && rfac_part_stride != (int64_t)P * P) {
+    set_error("dlsa_glm_rows_batched: rfac_part_stride must be 0 or P * P");
+    return DLSA_E_INVALID;
+  }
+  if (leverage && !rfac) {
+    set_error("dlsa_glm_rows_batched: leverage needs rfac");
+    return DLSA_E_INVALID;
+  }
+  const int64_t n_total = offsets[K];
+  if (n_total > 0 && (!X || !y)) {
+    set_error("null X or y");
+    return DLSA_E_INVALID;
+  }
+  Plan pl;
+  make_plan(offsets, K, p, fit_intercept, rows_per_chunk, pl);
+  if (pl.n_chunks == 0) return DLSA_OK;  // nothing to write
+  const int64_t nc = pl.n_chunks;
+  Bump b;
+  const int64_t off_row0 = b.take(8 * nc), off_rows = b.take(4 * nc), off_part = b.take(4 * nc);
+  const int64_t off_pcb = b.take(4LL * (K + 1));
+  Workspace ws(stream);
+  rc = ws.alloc(b.o);
+  if (rc != DLSA_OK) return rc;
+  int64_t* d_row0 = (int64_t*)ws.at(off_row0);
+  int32_t* d_rows = (int32_t*)ws.at(off_rows);
+  int32_t* d_part = (int32_t*)ws.at(off_part);
+  int32_t* d_pcb = (int32_t*)ws.at(off_pcb);
+  DLSA_HIP_TRY(upload_eval_plan(pl, K, d_row0, d_rows, d_part, d_pcb, stream));
+  RowsArgs ra;
+  memset(&ra, 0, sizeof(ra));
+  ra.P = P;
+  ra.X = X;
+  ra.y = y;
+  ra.chunk_row0 = d_row0;
+  ra.chunk_rows = d_rows;
+  ra.chunk_part = d_part;
+  ra.center = center;
+  ra.scale = scale;
+  ra.betas = betas;
+  ra.eta_offset = eta_offset;
+  ra.row_weight = row_weight;
+  ra.p = p;
+  set_stream_bounds(ra, n_total);
+  ra.intercept = fit_intercept ? 1 : 0;
+  ra.nbeta = 1;
+  ra.beta_part_stride = beta_part_stride;
+  ra.rfac = rfac;
+  ra.rfac_part_stride = rfac_part_stride;
+  ra.eta = eta;
+  ra.mu = mu;
+  ra.dev_res = dev_res;
+  ra.pearson_res = pearson_res;
+  ra.leverage = leverage;
+  DLSA_HIP_TRY(launch_rows_pass(ra, family, pl.n_chunks, stream));
+  DLSA_HIP_TRY(hipStreamSynchronize(stream));
+  return DLSA_OK;
+}
+
+int dlsa_glm_rows_batched(int32_t family, const double* X, const double* y,
+                          const double* eta_offset, const double* row_weight,
+                          const int64_t* offsets, int32_t K, int32_t p, int32_t fit_intercept,
+                          const double* center, const double* scale, const double* betas,
+                          int64_t beta_part_stride, const double* rfac,
+                          int64_t rfac_part_stride, double* eta, double* mu, double* dev_res,
+                          double* pearson_res, double* leverage, void* stream) {
+  return rows_dense(family, X, y, eta_offset, row_weight, offsets, K, p, fit_intercept, center,
+                    scale, betas, beta_part_stride, rfac, rfac_part_stride, 0, eta, mu, dev_res,
+                    pearson_res, leverage, stream);
+}
+
+int dlsa_glm_rows_batched_chunked(int32_t family, const double* X, const double* y,
+                                  const double* eta_offset, const double* row_weight,
+                                  const int64_t* offsets, int32_t K, int32_t p,
+                                  int32_t fit_intercept, const double* center,
+                                  const double* scale, const double* betas,
+                                  int64_t beta_part_stride, const double* rfac,
+                                  int64_t rfac_part_stride, int32_t rows_per_chunk, double* eta,
+                                  double* mu, double* dev_res, double* pearson_res,
+                                  double* leverage, void* stream) {
+  return rows_dense(family, X, y, eta_offset, row_weight, offsets, K, p, fit_intercept, center,
+                    scale, betas, beta_part_stride, rfac, rfac_part_stride, rows_per_chunk, eta,
+                    mu, dev_res, pearson_res, leverage, stream);
+}
+
 int dlsa_glm_gof_categorical(int32_t family, const double* Xn, const uint8_t* codes,
                              const double* y, const double* eta_offset,
                              const double* row_weight, const int64_t* offsets, int32_t K,

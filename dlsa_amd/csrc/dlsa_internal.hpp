@@ -458,6 +458,21 @@ hipError_t launch_score_pass(const GramArgs& a, int family, int n_chunks, hipStr
 hipError_t launch_gram_reduce(const GramArgs& a, const int32_t* pcb, int K, double* gram,
                               double* score, double* gram_sum, double* score_sum, hipStream_t s);
 
+// Row diagnostics pass (rows_pass_impl.hpp): per row eta, mu, the signed
+// deviance and Pearson residuals and the leverage omega w |R_k x|^2, at one
+// coefficient vector (betas + k * beta_part_stride, stride 0 or P) and one
+// lower-triangular factor R_k, R_k^T R_k = S_k^-1 (rfac + k * rfac_part_stride,
+// stride 0 or P P), per partition.  Each output is [n_total] or null; rfac may
+// be null only if leverage is.  No chunk partials: `partial` is unused.
+struct RowsArgs : EvalArgsWgt {
+  int64_t beta_part_stride;
+  const double* rfac;
+  int64_t rfac_part_stride;
+  double *eta, *mu, *dev_res, *pearson_res, *leverage;
+};
+// (sets nslot and slot_bytes itself)
+hipError_t launch_rows_pass(const RowsArgs& a, int family, int n_chunks, hipStream_t s);
+
 // Wide-P path (DLSA_MAX_P_FUSED < P <= DLSA_MAX_P, wide_exact.hip): a row
 // pass (eta, weights, gradient, log-lik) and a separate Gram pass over
 // 128x128 output tiles of the padded PP = 128 * NB Hessian.

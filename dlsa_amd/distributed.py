@@ -225,7 +225,7 @@ def sandwich_cov(A, M):
     return cov, 0.5 * (info + info.T)
 
 
-_COV_TYPES = (None, "model", "HC0", "HC1")
+_COV_TYPES = (None, "model", "HC0", "HC1", "HC3")
 
 
 def _cov_summary(out, cov, wlse):
@@ -242,12 +242,14 @@ def _cov_summary(out, cov, wlse):
 
 
 def _meat_sum(fit, X, y, offsets, family, eta_offset, exposure, sample_weight, fit_intercept,
-              center, scale, group):
+              center, scale, group, meat_weight=None):
     """sum_k M_k over the partitions the combine counts (status ok or maxiter)
     and over the ranks -- one score pass at each partition's own ``fit.theta``
     row, the others zeroed before the sum, one all-reduce -- with, in the same
     buffer, n+ (the rows with omega > 0 of those partitions; one more
     goodness-of-fit pass only when weights are given) and their count K_ok.
+    ``meat_weight``: None, or the weight the score pass takes in place of
+    ``sample_weight`` (HC3's omega / (1 - h)); n+ keeps counting omega > 0.
     Returns (M [P, P], n+, K_ok)."""
     import torch
 
@@ -256,7 +258,11 @@ def _meat_sum(fit, X, y, offsets, family, eta_offset, exposure, sample_weight, f
     kw = dict(thetas=fit.theta, eta_offset=eta_offset, exposure=exposure,
               sample_weight=sample_weight, fit_intercept=fit_intercept, center=center,
               scale=scale)
-    g = glm_gram_batched(family, X, y, offsets, kind="score", **kw)
+    if meat_weight is None:
+        g = glm_gram_batched(family, X, y, offsets, kind="score", **kw)
+    else:
+        g = glm_gram_batched(family, X, y, offsets, kind="score",
+                             **dict(kw, sample_weight=meat_weight))
     ok = fit.status <= 1
     zero = torch.zeros((), dtype=torch.float64, device=ok.device)
     M = torch.where(ok[:, None, None], g["gram"], zero).sum(0)
@@ -270,6 +276,39 @@ def _meat_sum(fit, X, y, offsets, family, eta_offset, exposure, sample_weight, f
                   group).cpu().numpy()
     P = fit.P
     return tot[:P * P].reshape(P, P).copy(), float(tot[-2]), float(tot[-1])
+
+
+def _hc3_weight(fit, X, y, offsets, family, eta_offset, exposure, sample_weight, fit_intercept,
+                center, scale):
+    """omega / (1 - h), the row weight whose score pass gives the HC3 meat
+    sum_i s_i^2 / (1 - h_i)^2 x_i x_i^T (mu does not depend on omega): one rows
+    pass at each partition's own ``fit.theta`` and ``fit.sig_inv``, the local
+    leverage.  A partition the combine counts (status ok or maxiter) with a
+    row where omega > 0 and h is not finite or 1 - h <= 0 raises
+    ``ValueError``: HC3 is undefined there.  The rows of the other partitions
+    get the weight 0 (their meat is not counted)."""
+    import torch
+
+    from .models import glm_rows_batched
+
+    h = glm_rows_batched(family, X, y, offsets, thetas=fit.theta, info=fit.sig_inv,
+                         outputs=("leverage",), eta_offset=eta_offset, exposure=exposure,
+                         sample_weight=sample_weight, fit_intercept=fit_intercept, center=center,
+                         scale=scale)["leverage"]
+    f64 = dict(dtype=torch.float64, device=h.device)
+    om = (torch.ones_like(h) if sample_weight is None
+          else torch.as_tensor(sample_weight, **f64).reshape(-1))
+    offs = torch.as_tensor(np.asarray(offsets, dtype=np.int64), device=h.device)
+    part = torch.repeat_interleave(torch.arange(offs.numel() - 1, device=h.device),
+                                   offs[1:] - offs[:-1])
+    counted = (fit.status <= 1).to(h.device)[part]
+    bad = counted & (om > 0) & ~(torch.isfinite(h) & (h < 1.0))
+    if bool(bad.any()):
+        k = int(part[bad][0])
+        raise ValueError(f"cov_type='HC3': partition {k} has a row with a positive weight whose "
+                         "leverage h is not finite or not below 1; HC3 is undefined there")
+    zero = torch.zeros((), **f64)
+    return torch.where(counted & (om > 0), om / (1.0 - h), zero)
 
 
 def _pearson_dispersion(fit, X, y, offsets, codes, levels, family, eta_offset, exposure,
@@ -358,7 +397,17 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
       weights one more goodness-of-fit pass counts them).  A non-positive
       denominator raises ``ValueError``.
 
-    "HC0" / "HC1" with ``dispersion="pearson"`` raise ``ValueError`` (the
+    * "HC3": HC0 with every row's s_i^2 divided by (1 - h_i)^2 (R's
+      ``sandwich::vcovHC`` default), h_i = omega_i w_i x_i^T Sig_inv_k^-1 x_i
+      the leverage against the row's own partition: with n split over K
+      partitions it is K times a pooled fit's, so the correction matters
+      exactly here.  One rows pass (``glm_rows_batched``, leverages only) and
+      the score pass with the weight omega / (1 - h).  A counted partition
+      with a row where omega > 0 and 1 - h <= 0 or h is not finite raises
+      ``ValueError``.  (HC2: ``glm_rows_batched``'s ``leverage`` and a score
+      pass with ``sample_weight = omega / sqrt(1 - h)``.)
+
+    "HC0" / "HC1" / "HC3" with ``dispersion="pearson"`` raise ``ValueError`` (the
     sandwich already absorbs phi), and with ``codes=`` too: the score pass
     covers the dense layout only.
     """
@@ -375,8 +424,9 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
     if dispersion not in (None, "pearson"):
         raise ValueError(f"dispersion must be None or 'pearson', not {dispersion!r}")
     if cov_type not in _COV_TYPES:
-        raise ValueError(f"cov_type must be None, 'model', 'HC0' or 'HC1', not {cov_type!r}")
-    robust = cov_type in ("HC0", "HC1")
+        raise ValueError("cov_type must be None, 'model', 'HC0', 'HC1' or 'HC3', not "
+                         f"{cov_type!r}")
+    robust = cov_type in ("HC0", "HC1", "HC3")
     if robust and dispersion is not None:
         raise ValueError(f"cov_type={cov_type!r} with dispersion='pearson': the sandwich already "
                          "absorbs the dispersion; give one of them")
@@ -414,8 +464,15 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
         fit = logistic_model_batched(X, y, offsets, fit_intercept=fit_intercept, **fit_kw)
     buf = reduce_partitions_device(fit, n_rows=True)
     if robust:
-        M, npos, k_ok = _meat_sum(fit, X, y, offsets, family, eta_offset, exposure, sample_weight,
-                                  fit_intercept, fit_kw.get("center"), fit_kw.get("scale"), group)
+        cs = (fit_kw.get("center"), fit_kw.get("scale"))
+        if cov_type == "HC3":
+            mw = _hc3_weight(fit, X, y, offsets, family, eta_offset, exposure, sample_weight,
+                             fit_intercept, *cs)
+            M, npos, k_ok = _meat_sum(fit, X, y, offsets, family, eta_offset, exposure,
+                                      sample_weight, fit_intercept, *cs, group, meat_weight=mw)
+        else:
+            M, npos, k_ok = _meat_sum(fit, X, y, offsets, family, eta_offset, exposure,
+                                      sample_weight, fit_intercept, *cs, group)
         b = combine(buf, group).cpu().numpy()
         S, v, st, K = split_reduced(b[:-1], fit.P)
         factor = 1.0

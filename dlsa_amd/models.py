@@ -1103,6 +1103,122 @@ def glm_gram_batched(family, X, y, offsets, thetas=None, beta=None, kind="score"
     return out
 
 
+_ROWS_STREAMS = ("eta", "mu", "dev_res", "pearson_res", "leverage")  # the C entry's order
+_ROWS_OUTPUTS = _ROWS_STREAMS + ("cooks",)
+
+
+def rows_factor(info, K, P):
+    """The factors R_k of the leverage pass from information matrices, on the
+    host (batched numpy): ``info`` [K, P, P] or [P, P] (symmetric; the lower
+    triangle is used), S_k = L L^T, R_k = L^-1, so that R_k^T R_k = S_k^-1 and
+    x^T S_k^-1 x = |R_k x|^2.  Returns [K, P, P] or [P, P], lower triangular
+    with an exactly zero upper triangle.  A matrix that is not finite or not
+    positive definite (an empty or failed partition's zeros) gives a NaN
+    factor: its partition's leverages are NaN, the others untouched."""
+    S = np.array(info, dtype=np.float64)
+    shared = S.ndim == 2
+    S = S.reshape(-1, P, P)
+    R = np.full_like(S, np.nan)
+    idx = np.flatnonzero(np.isfinite(S).all(axis=(1, 2)))
+    try:  # all at once; one by one only when some matrix is not positive definite
+        Ls = dict(zip(idx, np.linalg.cholesky(S[idx]))) if idx.size else {}
+    except np.linalg.LinAlgError:
+        Ls = {}
+        for k in idx:
+            try:
+                Ls[k] = np.linalg.cholesky(S[k])
+            except np.linalg.LinAlgError:
+                pass
+    # a pivot at rounding level: a rank-deficient matrix that rounding let through
+    tiny = P * np.finfo(np.float64).eps
+    idx = np.array([k for k, L in Ls.items()
+                    if np.min(np.diag(L)) ** 2 > tiny * np.max(np.diag(S[k]))], dtype=np.int64)
+    if idx.size:
+        Rs = np.tril(np.linalg.solve(np.stack([Ls[k] for k in idx]), np.eye(P)))
+        fin = np.isfinite(Rs).all(axis=(1, 2))
+        R[idx[fin]] = Rs[fin]
+    return R[0] if shared else R
+
+
+def glm_rows_batched(family, X, y, offsets, thetas=None, beta=None, info=None, outputs=None,
+                     eta_offset=None, exposure=None, sample_weight=None, fit_intercept=False,
+                     center=None, scale=None, rows_per_chunk=0, device=None):
+    """Per-row diagnostics of a GLM in one more pass over X (8 (p + 1) bytes
+    per row plus 8 per row extra read, 8 per output written;
+    ``dlsa_glm_rows_batched``, fp64 MFMA): what R's ``predict``, ``residuals``,
+    ``hatvalues`` and ``cooks.distance`` return, for the rows that were fitted.
+    A dict of [n] device tensors out of
+
+    * ``eta`` (the linear predictor, offset included) and ``mu``;
+    * ``dev_res``, ``pearson_res``: the signed deviance and Pearson residuals,
+      the square roots of ``glm_gof_batched``'s row terms (omega included)
+      with the sign of y - mu;
+    * ``leverage`` h_i = omega_i w_i x_i^T S_k^-1 x_i and ``cooks`` =
+      pearson_res^2 h / (P (1 - h)^2) -- only with ``info``, the information
+      matrix S_k the leverage is taken against: [K, P, P] (each partition
+      against its own, e.g. ``fit.sig_inv``: the local leverage of DLSA) or
+      [P, P] (one for all).  It is factored on the host (``rows_factor``); a
+      partition whose matrix is not finite or not positive definite gets NaN
+      leverages, the others are untouched.
+
+    ``outputs``: the names wanted (None: all that ``info`` allows).  Exactly one
+    of ``thetas`` [K, P] and ``beta`` [P]; ``family``, ``eta_offset`` /
+    ``exposure``, ``sample_weight``, ``center`` / ``scale``, the limit P <= 192
+    and the ``ValueError`` cases as in ``glm_gram_batched``.  Every value of a
+    row depends on that row, its partition's coefficients and factor alone:
+    the bits are the same from call to call and for every ``rows_per_chunk``."""
+    if (beta is None) == (thetas is None):
+        raise ValueError("give exactly one of thetas [K, P] (each partition at its own row) and "
+                         "beta [P] (every partition at the same vector)")
+    fam = _check_gof_args(family, X, beta, thetas, eta_offset, exposure, sample_weight)
+    if int(rows_per_chunk) < 0:
+        raise ValueError("rows_per_chunk must be >= 0")
+    if outputs is None:
+        outputs = _ROWS_OUTPUTS if info is not None else _ROWS_STREAMS[:4]
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    unknown = [o for o in outputs if o not in _ROWS_OUTPUTS]
+    if unknown or not outputs:
+        raise ValueError(f"outputs must be names out of {_ROWS_OUTPUTS}, not {unknown}")
+    if info is None and ("leverage" in outputs or "cooks" in outputs):
+        raise ValueError("leverage and cooks need info, the information matrix they are taken "
+                         "against ([K, P, P] or [P, P], e.g. fit.sig_inv)")
+    n, p = _shape(X)
+    P = p + (1 if fit_intercept else 0)
+    K = _size(offsets) - 1
+    coef = thetas if beta is None else beta
+    if beta is not None and _size(coef) != P:
+        raise ValueError("beta must be [P]: one coefficient vector for every partition")
+    if thetas is not None and (_size(coef) != K * P or
+                               (len(_shape(coef)) == 2 and _shape(coef) != (K, P))):
+        raise ValueError("thetas must be [K, P]: one row per partition")
+    if info is not None and _shape(info) not in ((K, P, P), (P, P)):
+        raise ValueError("info must be [K, P, P] (one information matrix per partition) or [P, P]")
+    dev, Xd, yd, offs, cd, sd = _dense_inputs(X, y, offsets, center, scale, device)
+    od, wd = _gof_extras(family, eta_offset, exposure, sample_weight, dev)
+    bd = _dev_f64(coef, dev).reshape(-1)
+    want = set(outputs)
+    if "cooks" in want:
+        want |= {"pearson_res", "leverage"}
+    rd, rstride = None, 0
+    if "leverage" in want:
+        host = info.detach().cpu().numpy() if isinstance(info, torch.Tensor) else info
+        R = rows_factor(host, K, P)
+        rstride = P * P if R.ndim == 3 else 0
+        rd = _dev_f64(R, dev).reshape(-1)
+    f64 = dict(dtype=torch.float64, device=dev)
+    bufs = {name: (torch.empty((n,), **f64) if name in want else None) for name in _ROWS_STREAMS}
+    rc = _hip.load().dlsa_glm_rows_batched_chunked(
+        fam, _ptr(Xd), _ptr(yd), _ptr(od), _ptr(wd), offs.ctypes.data_as(ctypes.c_void_p), K, p,
+        int(bool(fit_intercept)), _ptr(cd), _ptr(sd), _ptr(bd), P if thetas is not None else 0,
+        _ptr(rd), rstride, int(rows_per_chunk), *[_ptr(bufs[name]) for name in _ROWS_STREAMS],
+        _stream(dev))
+    _hip.check(rc, "dlsa_glm_rows_batched")
+    if "cooks" in want:
+        h, r = bufs["leverage"], bufs["pearson_res"]
+        bufs["cooks"] = r * r * h / (P * (1.0 - h) ** 2)
+    return {name: bufs[name] for name in outputs}
+
+
 # ---------------------------------------------------------------------------
 # reference-signature wrapper (one Spark group)
 # ---------------------------------------------------------------------------

@@ -725,6 +725,49 @@ int dlsa_glm_gram_batched_chunked(int32_t family, int32_t kind, const double* X,
                                   void* stream);
 
 /*
+ * Row diagnostics: one more pass over the dense layout (8 (p + 1) bytes per
+ * row plus 8 per row extra read, each once; 8 per requested output written)
+ * that gives, per row i of partition k at its coefficient vector beta_k:
+ *   eta[i]         x_i . beta_k (+ eta_offset_i)
+ *   mu[i]          the family's mean
+ *   dev_res[i]     sign(y_i - mu_i) sqrt(max(d_i, 0)), d_i the row's deviance
+ *   pearson_res[i] sign(y_i - mu_i) sqrt(chi_i), chi_i the row's Pearson term
+ *                  (the row terms of dlsa_glm_gof_batched, omega included)
+ *   leverage[i]    h_i = omega_i w_i |R_k x_i|^2 = omega_i w_i x_i^T S_k^-1 x_i
+ * with x_i, omega_i, w_i as in dlsa_glm_gram_batched.  rfac: the factor R_k,
+ * [P, P] row-major, lower triangular (the upper triangle is read and must be
+ * 0), R_k^T R_k = S_k^-1 -- the inverse of the Cholesky factor of S_k.
+ * rfac_part_stride: 0 (one R for every partition) or P P (rfac is [K, P, P]);
+ * betas, beta_part_stride as in dlsa_glm_gram_batched.  Any other stride is
+ * DLSA_E_INVALID.  Each of the five outputs is [n_total] fp64, device, or
+ * NULL (not computed); rfac may be NULL only if leverage is.  A non-finite
+ * R_k gives NaN leverages in partition k alone.
+ * family, eta_offset, row_weight, center / scale, the limit P <=
+ * DLSA_MAX_P_FUSED and the error cases are dlsa_glm_gram_batched's, checked
+ * before any launch.  An empty partition writes nothing.  Every value of a row
+ * depends on that row, beta_k and R_k alone, in one summation order: the bits
+ * are the same from call to call and for every rows_per_chunk.
+ */
+int dlsa_glm_rows_batched(int32_t family, const double* X, const double* y,
+                          const double* eta_offset, const double* row_weight,
+                          const int64_t* offsets, int32_t K, int32_t p, int32_t fit_intercept,
+                          const double* center, const double* scale, const double* betas,
+                          int64_t beta_part_stride, const double* rfac,
+                          int64_t rfac_part_stride, double* eta, double* mu, double* dev_res,
+                          double* pearson_res, double* leverage, void* stream);
+/* ... with the rows of a chunk chosen by the caller; rows_per_chunk = 0:
+ * automatic, as above. */
+int dlsa_glm_rows_batched_chunked(int32_t family, const double* X, const double* y,
+                                  const double* eta_offset, const double* row_weight,
+                                  const int64_t* offsets, int32_t K, int32_t p,
+                                  int32_t fit_intercept, const double* center,
+                                  const double* scale, const double* betas,
+                                  int64_t beta_part_stride, const double* rfac,
+                                  int64_t rfac_part_stride, int32_t rows_per_chunk, double* eta,
+                                  double* mu, double* dev_res, double* pearson_res,
+                                  double* leverage, void* stream);
+
+/*
  * dlsa_glm_gof_batched on the categorical-code layout of
  * dlsa_logistic_loglik_categorical (its arguments, limits and error cases: a
  * code >= levels[f] fails the call with DLSA_E_INVALID): the values the dense
