@@ -140,7 +140,8 @@ int fit_categorical(int family, const double* Xn, const uint8_t* codes, const do
   // only, so the first full pass after it would take the analytic bound's
   // coarse grid and could be the published one
   if (pois) opt.warm_start = 0;
-  const std::vector<Plan> plans = level_plans(offsets, K, P - ic, ic, opt.warm_start != 0, cat_rpc);
+  const std::vector<Plan> plans =
+      level_plans(offsets, K, P - ic, ic, opt.warm_start != 0, cat_rpc, /*x_cols=*/q);
   const Plan& pl = plans.back();
   const int64_t nc = std::max(pl.n_chunks, 1);
   // the fused layout for the most chunks of any level, then the presence

@@ -145,10 +145,11 @@ hipError_t FusedFit::pass(int ph, const Plan& q, bool full, const std::vector<in
       return launch_irls_wave(ps, q.NT, standardize, family, q.n_chunks, stream);
     }
     // OLS (one pass at theta = 0): X streamed into registers, no LDS ring.
-    // Its buffer range and row offsets are 32-bit: a caller's rows_per_chunk
-    // of >= 2^31 bytes per chunk takes the per-wave kernel instead
+    // Its buffer range and row offsets are 32-bit, like those of the kernels
+    // below (there is no kernel to fall back to for a longer chunk): make_plan
+    // keeps every chunk's X within kMaxChunkBytes, which this restates
     if (f64 && !rules.iterates && ols_stream_applies(q.NT) &&
-        (int64_t)q.max_chunk_rows * f.p * 8 < (1LL << 31))
+        (int64_t)q.max_chunk_rows * f.p * 8 <= kMaxChunkBytes)
       return launch_ols_stream(pc, q.NT, standardize, q.n_chunks, stream);
     if (wave) return launch_irls_wave(pc, q.NT, standardize, family, q.n_chunks, stream);
     return launch_irls_coop(pc, q.NT, prec, standardize, family, q.n_chunks, stream);

@@ -127,8 +127,28 @@ inline int64_t level_rows(const int64_t* offsets, int K, double frac, int64_t mi
   return n;
 }
 
+// The longest chunk any plan holds.  The fused passes (irls_coop_impl.hpp,
+// irls_wave_impl.hpp, irls_oz_impl.hpp, ols_stream.hip) read a chunk's X
+// through one raw buffer resource of at most 0x7FFFFFF0 bytes (uniform_rsrc)
+// with 32-bit offsets from the chunk's first 16-byte boundary, and a load past
+// the resource's end returns zeros instead of faulting: a longer chunk would
+// be fitted with its later rows read as zero rows.  So a chunk's X stays under
+// 2^31 bytes less 1 MiB: the room holds the 15 bytes of alignment slack in
+// front and what the last block's pieces read behind the chunk's last row
+// (less than one LDS slot, 160 KiB), so that every offset a block forms stays a
+// positive int inside the resource.  The automatic sizes (at most 131072 rows
+// of DLSA_MAX_P columns: 2^29 bytes) never get here; a caller's rows_per_chunk
+// can, and is then a hint: make_plan splits evenly into more chunks.
+constexpr int64_t kMaxChunkBytes = (int64_t(1) << 31) - (int64_t(1) << 20);
+inline int64_t max_chunk_rows(int p) {
+  return std::max<int64_t>(1, kMaxChunkBytes / (8LL * std::max(p, 1)));
+}
+
+// x_cols: the doubles of a row in memory, which the cap on a chunk's bytes
+// counts (-1: p, the dense layout; the categorical-code layout holds its q
+// numeric columns, not the P - intercept columns of the expanded design).
 inline bool make_plan(const int64_t* offsets, int K, int p, int intercept, int rows_per_chunk,
-                      Plan& pl, double frac = 1.0, int64_t min_rows = 0) {
+                      Plan& pl, double frac = 1.0, int64_t min_rows = 0, int x_cols = -1) {
   pl.P = p + (intercept ? 1 : 0);
   pl.NT = (pl.P + 15) / 16;
   pl.T = pl.NT * (pl.NT + 1) / 2;
@@ -136,7 +156,9 @@ inline bool make_plan(const int64_t* offsets, int K, int p, int intercept, int r
   // fused pass: chunk size from all rows (a warm-start level keeps the full
   // pass's chunk size: fewer, equally long chunks -- measured as fast)
   const int64_t n_total = offsets[K];
-  const int rpc = rows_per_chunk > 0 ? rows_per_chunk : auto_rows_per_chunk(n_total);
+  const int64_t rpc = std::min<int64_t>(
+      rows_per_chunk > 0 ? rows_per_chunk : auto_rows_per_chunk(n_total),
+      max_chunk_rows(x_cols >= 0 ? x_cols : p));
   pl.part_chunk_begin.assign(K + 1, 0);
   pl.chunk_row0.clear();
   pl.chunk_rows.clear();
@@ -168,20 +190,21 @@ inline bool make_plan(const int64_t* offsets, int K, int p, int intercept, int r
 // rows_per_chunk(frac, min_rows) is make_plan's rows_per_chunk for that level.
 template <typename RowsPerChunk>
 std::vector<Plan> level_plans(const int64_t* offsets, int K, int p, int intercept, bool levels,
-                              RowsPerChunk rows_per_chunk) {
+                              RowsPerChunk rows_per_chunk, int x_cols = -1) {
   std::vector<Plan> plans;
   if (levels) {
     const int P = p + (intercept ? 1 : 0);
     const int64_t min_rows = std::max<int64_t>(2048, level_rows_per_param() * P);
     for (double frac : warm_level_fracs(true)) {
       Plan q;
-      make_plan(offsets, K, p, intercept, rows_per_chunk(frac, min_rows), q, frac, min_rows);
+      make_plan(offsets, K, p, intercept, rows_per_chunk(frac, min_rows), q, frac, min_rows,
+                x_cols);
       if (level_rows(offsets, K, frac, min_rows) <= offsets[K] / 2 && q.n_chunks > 0)
         plans.push_back(std::move(q));
     }
   }
   Plan full;
-  make_plan(offsets, K, p, intercept, rows_per_chunk(1.0, 0), full);
+  make_plan(offsets, K, p, intercept, rows_per_chunk(1.0, 0), full, 1.0, 0, x_cols);
   plans.push_back(std::move(full));
   return plans;
 }
@@ -261,7 +284,8 @@ inline void make_wide_plans(const int64_t* offsets, int K, int p, int intercept,
                                                                 int64_t(1) << 24));
   if (rows_per_chunk > 0) rpc_row = rpc_gram = rows_per_chunk;
   if (const char* e = env_knob("DLSA_WIDE_GRAM_ROWS")) rpc_gram = std::max(64, atoi(e));
-  // the Gram kernels address a row group's X with 32-bit buffer offsets
+  // the Gram kernels address a row group's X with 32-bit buffer offsets: half
+  // of what make_plan allows every chunk (kMaxChunkBytes), which the row plan gets
   rpc_gram = (int)std::min<int64_t>(rpc_gram, (int64_t(1) << 30) / (8LL * std::max(p, 1)));
   make_plan(offsets, K, p, intercept, rpc_row, wp.rows, frac, min_rows);
   make_plan(offsets, K, p, intercept, rpc_gram, wp.gram, frac, min_rows);

@@ -119,7 +119,19 @@ typedef struct dlsa_fit_options {
                                pass (<= 0: default 1e-6) */
   void* workspace;          /* device scratch, NULL: allocate per call */
   int64_t workspace_bytes;  /* size of `workspace` */
-  int32_t rows_per_chunk;   /* <= 0: automatic (rows one workgroup streams) */
+  int32_t rows_per_chunk;   /* <= 0: automatic (rows one workgroup streams).
+                               A tuning hint, here and in every entry that takes
+                               one: a chunk holds at most (2^31 - 2^20) / (8 p)
+                               rows, so that its X (p columns, 8 p bytes per
+                               row) stays inside one 2 GiB buffer range with
+                               32-bit offsets.  A partition asked for in longer
+                               chunks is split evenly into ceil(n_k / that
+                               limit) or more of them
+                               (dlsa_fit_stats.n_chunks,
+                               dlsa_logistic_workspace_bytes count these).
+                               Sums depend on the chunking in their last bits,
+                               as for any other rows_per_chunk; the per-row
+                               outputs of dlsa_glm_rows_batched do not */
   int32_t warm_start;       /* 1 (default): the first Newton iterations run on
                                row prefixes of each partition (1/16, then 1/4
                                of the rows, never fewer than max(2048, 64 P))

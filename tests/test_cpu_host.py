@@ -75,6 +75,45 @@ def test_workspace_bytes_table(sizes, p, fi, rpc, want):
     assert _workspace_bytes(offsets, p, fi, rpc) == want
 
 
+# the longest chunk of a plan (csrc/fit_plan.hpp: kMaxChunkBytes, max_chunk_rows)
+MAX_CHUNK_BYTES = 2**31 - 2**20
+
+
+def max_chunk_rows(p):
+    return MAX_CHUNK_BYTES // (8 * p)
+
+
+@pytest.mark.parametrize("p,fi", [(191, 1), (512, 0)], ids=["fused-P192", "wide-p512"])
+def test_workspace_bytes_long_chunks_are_split(p, fi):
+    """rows_per_chunk is a hint above max_chunk_rows(p): one partition of n
+    rows, max_chunk_rows < n < 2 max_chunk_rows, asked for as one chunk is
+    planned as the two chunks of rows_per_chunk = ceil(n / 2).  (The wide
+    path's Gram row groups have their own, tighter clamp: the same in both.)"""
+    m = max_chunk_rows(p)
+    n = m + m // 2
+    two = _workspace_bytes([0, n], p, fi, (n + 1) // 2)
+    assert two > 0
+    assert _workspace_bytes([0, n], p, fi, n) == two
+    assert _workspace_bytes([0, n], p, fi, 2**31 - 1) == two
+    # a second, short partition does not change that
+    assert _workspace_bytes([0, n, n + 3001], p, fi, n) == \
+        _workspace_bytes([0, n, n + 3001], p, fi, (n + 1) // 2)
+
+
+@pytest.mark.parametrize("p,fi", [(191, 1), (512, 0)], ids=["fused-P192", "wide-p512"])
+def test_workspace_bytes_largest_honoured_chunk(p, fi):
+    """max_chunk_rows(p) rows are honoured as one chunk -- not the two of half
+    as many rows per chunk -- and one row more is two."""
+    m = max_chunk_rows(p)
+    one, two = _workspace_bytes([0, m], p, fi, m), _workspace_bytes([0, m], p, fi, (m + 1) // 2)
+    assert 0 < one < two
+    assert _workspace_bytes([0, m + 1], p, fi, m + 1) == \
+        _workspace_bytes([0, m + 1], p, fi, (m + 2) // 2) > one
+    if p + fi <= 192:  # the fused layout depends on the chunk count alone
+        assert one == _workspace_bytes([0, 1000], p, fi, 1000)
+        assert two == _workspace_bytes([0, 1000], p, fi, 500)
+
+
 def test_workspace_bytes_rejects_decreasing_offsets():
     assert _workspace_bytes([0, 5, 3], 10, 1, 0) == -1
 
