@@ -173,6 +173,11 @@ SIGNATURES = {
         ctypes.c_int,
         [_I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _I32, _P, _P, _P, _P,
          _P]),
+    # ... on the categorical-code layout: Xn, codes, y; q, F, levels after K
+    "dlsa_glm_gram_categorical": (
+        ctypes.c_int,
+        [_I32, _I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I64, _I32,
+         _P, _P, _P, _P, _P]),
     # row diagnostics: family; eta_offset and row_weight after y; betas and its stride,
     # rfac and its stride; eta, mu, dev_res, pearson_res, leverage (the chunked entry:
     # rows_per_chunk after rfac's stride)

@@ -36,10 +36,15 @@ SOURCES = (["irls_coop.hip"] + [f"irls_coop_g{i}.hip" for i in range(1, 7)] +
            ["gof_pass.hip", "gof_cat_pass.hip", "gof_cat_pass_pois.hip"] +
            # score outer products (sandwich covariance): logistic, Poisson
            ["score_pass.hip", "score_pass_pois.hip"] +
+           # ... on the categorical-code layout: the gram-mode kernels of the categorical
+           # pass, one unit per (family, row-extras mask, kind), and the entry point
+           [f"cat_gram_{k}{t}.hip" for k in ("score", "info") for t in ("", "_wgt")] +
+           [f"cat_gram_pois_{k}{t}.hip" for k in ("score", "info")
+            for t in ("", "_ofs", "_wgt", "_ofs_wgt")] + ["gram_cat.hip"] +
            # row diagnostics (eta, mu, residuals, leverages): logistic, Poisson
            ["rows_pass.hip", "rows_pass_pois.hip"] +
            ["wide_exact.hip", "wide_fused.hip", "wide_newton.hip", "wide_oz.hip", "cat_pass.hip", "partition_rows.hip", "moments.hip", "ols_stream.hip", "eval_pass.hip", "eval_cat_pass.hip", "newton_solve.hip", "aux_kernels.hip", "fit_fused.hip", "fit_wide.hip", "fit_cat.hip", "capi.hip", "lars_host.cpp"])
-HEADERS = ["dlsa_internal.hpp", "newton_step.hpp", "wide_common.hpp", "fit_plan.hpp", "fit_driver.hpp", "wave_math.hpp", "glm_row.hpp", "irls_coop_impl.hpp", "irls_wave_impl.hpp", "irls_oz_impl.hpp", "eval_pass_impl.hpp", "cat_pass_impl.hpp", "cat_pois_impl.hpp", "eval_cat_pass_impl.hpp", "gof_pass_impl.hpp", "gof_cat_pass_impl.hpp", "score_pass_impl.hpp", "rows_pass_impl.hpp", os.path.join("..", "..", "include", "dlsa_hip.h")]
+HEADERS = ["dlsa_internal.hpp", "newton_step.hpp", "wide_common.hpp", "fit_plan.hpp", "fit_driver.hpp", "wave_math.hpp", "glm_row.hpp", "irls_coop_impl.hpp", "irls_wave_impl.hpp", "irls_oz_impl.hpp", "eval_pass_impl.hpp", "cat_pass_impl.hpp", "cat_pois_impl.hpp", "eval_cat_pass_impl.hpp", "gof_pass_impl.hpp", "gof_cat_pass_impl.hpp", "score_pass_impl.hpp", "rows_pass_impl.hpp", "cat_gram_impl.hpp", os.path.join("..", "..", "include", "dlsa_hip.h")]
 ARCH = os.environ.get("DLSA_OFFLOAD_ARCH", "gfx950")
 
 

@@ -1,0 +1,9 @@
+// Gram-mode kernels of the categorical pass (cat_gram_impl.hpp): the Poisson
+// family, the offset and prior weights, d = omega w.
+#include "cat_gram_impl.hpp"
+
+namespace dlsa {
+
+DLSA_CAT_GRAM_UNIT(FAMILY_POISSON, EX_OFS | EX_WGT, CAT_ROW_GRAM_INFORMATION)
+
+}  // namespace dlsa

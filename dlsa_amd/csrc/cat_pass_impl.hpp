@@ -113,11 +113,31 @@ __host__ __device__ __forceinline__ int cat_pair(int f, int g, int F) {
 // NaN hscale[0] marks a partition no grid can serve: the workgroup skips its
 // rows and publishes a NaN log-likelihood, which the solve takes as an
 // overshoot.
+// The row mode MODE travels in RX above the extras bits (cat_rx), so that the
+// Newton kernels keep their names and their code (tools/kernel_diff.py)
+// beside the gram kernels: CAT_ROW_NEWTON is the fit's pass above.  In a gram mode
+// (cat_gram*.hip, cat_gram_impl.hpp: the score outer-product pass of this
+// layout) the two row scalars are replaced after the link by res := s =
+// omega (y - mu) and w := d = s^2 (CAT_ROW_GRAM_SCORE) or omega w
+// (CAT_ROW_GRAM_INFORMATION), with (mu, w) from row_mean (glm_row.hpp); the
+// register triangle, the fixed-point terms, the histogram adds, the fold
+// factor and the slab epilogue below that point are used as they are, so the
+// slab holds sum d x x^T and sum s x.  A gram mode sums no log-likelihood,
+// writes no mumax and reads no phase; theta is [K, P], one coefficient vector
+// per partition; its grids are measured from the terms themselves before the
+// pass (cat_gram_impl.hpp), for either family, and a NaN hscale[0] (a
+// partition with a term that is not finite) makes the workgroup skip its rows
+// and write NaN into every slab value of its chunk.
+enum : int { CAT_ROW_NEWTON = 0, CAT_ROW_GRAM_SCORE = 1, CAT_ROW_GRAM_INFORMATION = 2 };
+constexpr int kCatRowModeShift = 4;
+constexpr int cat_rx(int extras, int mode) { return extras | (mode << kCatRowModeShift); }
 template <int QN, int FM, int NTHR, bool STD, bool EX, int FAM, int RX>
 __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
     const typename cat_pass_args_of<FAM, RX>::type a) {
   constexpr bool WGT = (RX & EX_WGT) != 0, OFS = (RX & EX_OFS) != 0;
   constexpr bool POIS = FAM == FAMILY_POISSON;
+  constexpr int MODE = RX >> kCatRowModeShift;
+  constexpr bool GRAM = MODE != CAT_ROW_NEWTON;
   static_assert(POIS || !OFS, "the offset is the Poisson family's");
   extern __shared__ __attribute__((aligned(16))) double sm[];
   constexpr int NW = NTHR / 64;
@@ -132,7 +152,8 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
   constexpr int NR = NTRI + NQ + 1;  // reduced register values: H block, gradient, ll
   const int chunk = blockIdx.x;
   const int part = a.chunk_part[chunk];
-  if (a.phase[part] != a.want_phase) return;  // workgroup-uniform
+  if constexpr (!GRAM)
+    if (a.phase[part] != a.want_phase) return;  // workgroup-uniform
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int q = EX ? QN - 1 : a.q, F = a.F, P = a.P, ic = EX ? 1 : a.intercept;
@@ -177,7 +198,7 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
 
   const int64_t row0 = a.chunk_row0[chunk];
   // (POIS: no rows for a partition whose grids could not be made)
-  const bool no_grid = POIS && isnan(a.hscale[(int64_t)part * (kCatQMax + 2)]);
+  const bool no_grid = (POIS || GRAM) && isnan(a.hscale[(int64_t)part * (kCatQMax + 2)]);
   const int nrows = no_grid ? 0 : a.chunk_rows[chunk];
   // fixed-point scales in registers (not re-read from the kernel arguments
   // inside the row loop): [0] w, [1] residual, [2 + i - ic] w x_i
@@ -282,7 +303,19 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
 #pragma unroll
     for (int f = 0; f < FM; ++f) e0 += de[f];
     double w, res;
-    if constexpr (POIS) {
+    if constexpr (GRAM) {
+      double e = e0 + e1;
+      if constexpr (OFS) e += ofl;
+      const RowMean k = row_mean<FAM>(e);
+      res = yv - k.mu;
+      if constexpr (WGT) res *= oml;
+      if constexpr (MODE == CAT_ROW_GRAM_SCORE) {
+        w = res * res;
+      } else {
+        w = k.w;
+        if constexpr (WGT) w *= oml;
+      }
+    } else if constexpr (POIS) {
       double e = e0 + e1;
       if constexpr (OFS) e += ofl;
       const double mu = exp(e);
@@ -393,7 +426,7 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
     const double v = wave_red(gacc[i]);
     if (lane == 0) red[wid * NR + NTRI + i] = v;
   }
-  {
+  if constexpr (!GRAM) {
     const double v = wave_red(llacc);
     if (lane == 0) red[wid * NR + NTRI + NQ] = v;
   }
@@ -414,7 +447,7 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
   // POIS: the waves' constant-term sums and largest mu, behind the grids
   constexpr int kLlcAt = 32, kMuAt = 48;
   static_assert(kCatQMax + 2 <= kLlcAt && kLlcAt + NW <= kMuAt && kMuAt + NW <= kCatPMax);
-  if constexpr (POIS) {
+  if constexpr (POIS && !GRAM) {
     const double v = wave_red(llcacc);
     unsigned long long m = mubits;
 #pragma unroll
@@ -494,6 +527,7 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
         }
       }
     }
+    if constexpr (GRAM) v = no_grid ? hsl[0] : v;  // (the NaN of hscale[0])
     dst[e] = v;
   }
   const int PP = 16 * NT;
@@ -509,9 +543,12 @@ __global__ __launch_bounds__(NTHR) void cat_pass_kernel(
       for (int rp = 0; rp <= r.x; ++rp) s += hist_at(hist, r.w + cat_slot(r, l, rp));
       v = (double)s / hsl[1];
     }
+    if constexpr (GRAM) v = no_grid ? hsl[0] : v;
     a.slab_g[(int64_t)chunk * PP + e] = v;
   }
-  if constexpr (POIS) {
+  if constexpr (GRAM) {
+    // (no log-likelihood, no mumax)
+  } else if constexpr (POIS) {
     if (tid == 0) {
       double c = 0.0;
       unsigned long long m = 0ull;

@@ -168,20 +168,24 @@ def combine_gram(gram_sum, score_sum, group=None):
 
 def gram_sharded(X, y, offsets, thetas=None, beta=None, kind="score", family="logistic",
                  eta_offset=None, exposure=None, sample_weight=None, fit_intercept=False,
-                 center=None, scale=None, rows_per_chunk=0, group=None):
+                 center=None, scale=None, rows_per_chunk=0, group=None, codes=None, levels=None):
     """``loglik_sharded`` for the score outer-product pass
     (``glm_gram_batched``, the same arguments; X, y, offsets describe the LOCAL
     shard): the sum over every partition of the job of the meat (``kind`` =
     "score") or the information matrix ("information") and of the score
-    vector.  ONE all-reduce of this rank's P^2 + P totals.  Returns a dict of
-    numpy arrays, the same on every rank: ``gram_sum`` [P, P], ``score_sum``
-    [P]."""
-    from .models import glm_gram_batched
+    vector.  With ``codes``/``levels`` X holds the numeric columns of the
+    categorical-code layout (``glm_gram_batched_categorical``).  ONE all-reduce
+    of this rank's P^2 + P totals.  Returns a dict of numpy arrays, the same on
+    every rank: ``gram_sum`` [P, P], ``score_sum`` [P]."""
+    from .models import glm_gram_batched, glm_gram_batched_categorical
 
-    g = glm_gram_batched(family, X, y, offsets, thetas=thetas, beta=beta, kind=kind,
-                         eta_offset=eta_offset, exposure=exposure, sample_weight=sample_weight,
-                         fit_intercept=fit_intercept, center=center, scale=scale,
-                         return_sum=True, rows_per_chunk=rows_per_chunk)
+    kw = dict(thetas=thetas, beta=beta, kind=kind, eta_offset=eta_offset, exposure=exposure,
+              sample_weight=sample_weight, fit_intercept=fit_intercept, center=center,
+              scale=scale, return_sum=True, rows_per_chunk=rows_per_chunk)
+    if codes is not None:
+        g = glm_gram_batched_categorical(family, X, codes, y, offsets, levels, **kw)
+    else:
+        g = glm_gram_batched(family, X, y, offsets, **kw)
     G, sc = combine_gram(g["gram_sum"], g["score_sum"], group)
     return {"gram_sum": G, "score_sum": sc}
 
@@ -242,7 +246,7 @@ def _cov_summary(out, cov, wlse):
 
 
 def _meat_sum(fit, X, y, offsets, family, eta_offset, exposure, sample_weight, fit_intercept,
-              center, scale, group, meat_weight=None):
+              center, scale, group, meat_weight=None, codes=None, levels=None):
     """sum_k M_k over the partitions the combine counts (status ok or maxiter)
     and over the ranks -- one score pass at each partition's own ``fit.theta``
     row, the others zeroed before the sum, one all-reduce -- with, in the same
@@ -250,15 +254,22 @@ def _meat_sum(fit, X, y, offsets, family, eta_offset, exposure, sample_weight, f
     goodness-of-fit pass only when weights are given) and their count K_ok.
     ``meat_weight``: None, or the weight the score pass takes in place of
     ``sample_weight`` (HC3's omega / (1 - h)); n+ keeps counting omega > 0.
+    ``codes`` / ``levels``: X holds the numeric columns of the categorical-code
+    layout, and the two passes are that layout's.
     Returns (M [P, P], n+, K_ok)."""
     import torch
 
-    from .models import glm_gof_batched, glm_gram_batched
+    from .models import (glm_gof_batched, glm_gof_batched_categorical, glm_gram_batched,
+                         glm_gram_batched_categorical)
 
     kw = dict(thetas=fit.theta, eta_offset=eta_offset, exposure=exposure,
               sample_weight=sample_weight, fit_intercept=fit_intercept, center=center,
               scale=scale)
-    if meat_weight is None:
+    if codes is not None:
+        g = glm_gram_batched_categorical(
+            family, X, codes, y, offsets, levels, kind="score",
+            **(kw if meat_weight is None else dict(kw, sample_weight=meat_weight)))
+    elif meat_weight is None:
         g = glm_gram_batched(family, X, y, offsets, kind="score", **kw)
     else:
         g = glm_gram_batched(family, X, y, offsets, kind="score",
@@ -266,7 +277,10 @@ def _meat_sum(fit, X, y, offsets, family, eta_offset, exposure, sample_weight, f
     ok = fit.status <= 1
     zero = torch.zeros((), dtype=torch.float64, device=ok.device)
     M = torch.where(ok[:, None, None], g["gram"], zero).sum(0)
-    if sample_weight is not None:
+    if sample_weight is not None and codes is not None:
+        rows = glm_gof_batched_categorical(family, X, codes, y, offsets, levels,
+                                           **kw)["n_pos"].to(torch.float64)
+    elif sample_weight is not None:
         rows = glm_gof_batched(family, X, y, offsets, **kw)["n_pos"].to(torch.float64)
     else:
         rows = torch.from_numpy(np.diff(np.asarray(offsets, dtype=np.int64)).astype(np.float64)
@@ -341,6 +355,73 @@ def _pearson_dispersion(fit, X, y, offsets, codes, levels, family, eta_offset, e
     return float(tot[0] / dof)
 
 
+def _sandwich_tail(fit, buf, M, npos, k_ok, cov_type, fit_intercept, lars_type, group):
+    """The robust tail of ``dlsa_fit_sharded`` and ``sandwich_sharded`` from
+    this rank's reduced buffer and the job's meat: the all-reduce, HC1's
+    factor, ``sandwich_cov``, ``finish`` on A M^-1 A and the coefficient
+    table."""
+    b = combine(buf, group).cpu().numpy()
+    S, v, st, K = split_reduced(b[:-1], fit.P)
+    factor = 1.0
+    if cov_type == "HC1":
+        dof = npos - k_ok * fit.P
+        if not dof > 0:
+            raise ValueError(f"cov_type='HC1': residual degrees of freedom {dof:g} = rows "
+                             "with a positive weight - fitted partitions x P is not positive")
+        factor = npos / dof
+    wlse = np.linalg.lstsq(S, v, rcond=None)[0]
+    cov, info = sandwich_cov(S, M * factor)
+    out = finish(info, info @ wlse, st, K, int(round(float(b[-1]))), fit_intercept, lars_type)
+    out.update(wlse=wlse, Sig_inv_sum=S, info=info, meat_sum=M)
+    _cov_summary(out, cov, wlse)
+    return out
+
+
+def sandwich_sharded(fit, X, y, offsets, cov_type="HC0", codes=None, levels=None,
+                     family="logistic", eta_offset=None, exposure=None, sample_weight=None,
+                     fit_intercept=False, center=None, scale=None, lars_type="lasso", group=None):
+    """The robust branch of ``dlsa_fit_sharded`` for an existing ``BatchedFit``
+    of this rank's partitions, on either layout: ``reduce_partitions_device``,
+    the meat at each partition's own ``fit.theta`` row over the partitions the
+    combine counts (status ok or maxiter), the all-reduces, ``sandwich_cov``,
+    the LARS / DBIC tail on A M^-1 A and the coefficient table.  X, y, offsets
+    and the keywords describe the LOCAL shard exactly as they were given to the
+    fit.  Returns the keys ``dlsa_fit_sharded(cov_type=...)`` returns except
+    ``"fit"``; on the dense layout they are the same bits.
+
+    With ``codes``/``levels`` X holds the numeric columns of the
+    categorical-code layout and the passes are
+    ``glm_gram_batched_categorical`` (and, for HC1's n+ with weights,
+    ``glm_gof_batched_categorical``).  ``dlsa_fit_sharded`` itself still
+    refuses ``cov_type`` with ``codes=``; the route on codes is
+
+        out = dlsa_fit_sharded(X, y, offsets, codes=codes, levels=levels, ...)
+        out.update(sandwich_sharded(out["fit"], X, y, offsets, codes=codes,
+                                    levels=levels, ...))
+
+    ``cov_type``: "HC0", "HC1" or, on the dense layout only, "HC3" (leverages
+    on the code layout are not computed yet: ``ValueError``); anything else
+    raises ``ValueError``."""
+    if cov_type not in ("HC0", "HC1", "HC3"):
+        raise ValueError(f"cov_type must be 'HC0', 'HC1' or 'HC3', not {cov_type!r}")
+    if family not in ("logistic", "poisson"):
+        raise ValueError(f"family must be 'logistic' or 'poisson', not {family!r}")
+    if (eta_offset is not None or exposure is not None) and family != "poisson":
+        raise ValueError("eta_offset / exposure need family='poisson'")
+    if cov_type == "HC3" and codes is not None:
+        raise ValueError("cov_type='HC3' with codes=: the leverages cover the dense layout only "
+                         "(the categorical-code layout is not supported yet)")
+    buf = reduce_partitions_device(fit, n_rows=True)
+    mw = None
+    if cov_type == "HC3":
+        mw = _hc3_weight(fit, X, y, offsets, family, eta_offset, exposure, sample_weight,
+                         fit_intercept, center, scale)
+    M, npos, k_ok = _meat_sum(fit, X, y, offsets, family, eta_offset, exposure, sample_weight,
+                              fit_intercept, center, scale, group, meat_weight=mw, codes=codes,
+                              levels=levels)
+    return _sandwich_tail(fit, buf, M, npos, k_ok, cov_type, fit_intercept, lars_type, group)
+
+
 def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
                      group=None, codes=None, levels=None, family="logistic", eta_offset=None,
                      exposure=None, dispersion=None, cov_type=None, sample_weight=None,
@@ -408,8 +489,10 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
       pass with ``sample_weight = omega / sqrt(1 - h)``.)
 
     "HC0" / "HC1" / "HC3" with ``dispersion="pearson"`` raise ``ValueError`` (the
-    sandwich already absorbs phi), and with ``codes=`` too: the score pass
-    covers the dense layout only.
+    sandwich already absorbs phi), and with ``codes=`` too: on the
+    categorical-code layout the robust covariance is one more call,
+    ``out.update(sandwich_sharded(out["fit"], X, y, offsets, codes=codes,
+    levels=levels, ...))`` ("HC0" / "HC1"; ``glm_gram_batched_categorical``).
     """
     from .models import (logistic_model_batched, logistic_model_batched_categorical,
                          logistic_model_batched_categorical_weighted,
@@ -473,20 +556,7 @@ def dlsa_fit_sharded(X, y, offsets, fit_intercept=False, lars_type="lasso",
         else:
             M, npos, k_ok = _meat_sum(fit, X, y, offsets, family, eta_offset, exposure,
                                       sample_weight, fit_intercept, *cs, group)
-        b = combine(buf, group).cpu().numpy()
-        S, v, st, K = split_reduced(b[:-1], fit.P)
-        factor = 1.0
-        if cov_type == "HC1":
-            dof = npos - k_ok * fit.P
-            if not dof > 0:
-                raise ValueError(f"cov_type='HC1': residual degrees of freedom {dof:g} = rows "
-                                 "with a positive weight - fitted partitions x P is not positive")
-            factor = npos / dof
-        wlse = np.linalg.lstsq(S, v, rcond=None)[0]
-        cov, info = sandwich_cov(S, M * factor)
-        out = finish(info, info @ wlse, st, K, int(round(float(b[-1]))), fit_intercept, lars_type)
-        out.update(wlse=wlse, Sig_inv_sum=S, info=info, meat_sum=M)
-        _cov_summary(out, cov, wlse)
+        out = _sandwich_tail(fit, buf, M, npos, k_ok, cov_type, fit_intercept, lars_type, group)
     elif dispersion is None:
         out = combine_and_finish(buf, fit.P, fit_intercept, lars_type, group)
     else:

@@ -1103,6 +1103,75 @@ def glm_gram_batched(family, X, y, offsets, thetas=None, beta=None, kind="score"
     return out
 
 
+def glm_gram_batched_categorical(family, Xn, codes, y, offsets, levels, thetas=None, beta=None,
+                                 kind="score", eta_offset=None, exposure=None,
+                                 sample_weight=None, fit_intercept=False, center=None,
+                                 scale=None, return_sum=False, rows_per_chunk=0, device=None):
+    """``glm_gram_batched`` on the categorical-code layout of
+    ``logistic_model_batched_categorical`` (same Xn / codes / levels / center /
+    scale and parameter order): the meat or the information matrix and the
+    score of the dummy-expanded design without building it
+    (``dlsa_glm_gram_categorical``), at 8 q + F + 8 bytes per row, streamed
+    twice, instead of 8 P.  The arguments, their ``ValueError`` cases and the
+    returned dict are ``glm_gram_batched``'s; the limits are the categorical
+    fit's (P <= 192, intercept + q <= 16, F <= 16, histograms that fit the
+    LDS), and a code >= levels[f] raises ``DlsaHipError``.
+
+    The one-hot blocks are fixed-point histogram sums on grids measured from
+    the rows' own terms at the given coefficients: an entry of a dummy row or
+    column of partition k is within n_k R 2^-60 B of the fp64-exact sum (R the
+    rows of the largest chunk, at least 1024; B the partition's largest |d|,
+    |s| or |d x_j|), the numeric block is summed in fp64, and two calls give
+    the same bits.  A partition with a term that is not finite (a NaN weight or
+    offset) gets an all-NaN ``gram`` and ``score``; no other partition is
+    touched."""
+    if kind not in _GRAM_KINDS:
+        raise ValueError(f"kind must be 'score' or 'information', not {kind!r}")
+    if (beta is None) == (thetas is None):
+        raise ValueError("give exactly one of thetas [K, P] (each partition at its own row) and "
+                         "beta [P] (every partition at the same vector)")
+    fam = _check_gof_args(family, Xn, beta, thetas, eta_offset, exposure, sample_weight)
+    if int(rows_per_chunk) < 0:
+        raise ValueError("rows_per_chunk must be >= 0")
+    q = _shape(Xn)[1]
+    lv = np.asarray(levels, dtype=np.int64).reshape(-1)
+    if len(_shape(codes)) != 2 or _shape(codes)[0] != _shape(Xn)[0]:
+        raise ValueError("codes must be [n, F]")
+    if lv.size != _shape(codes)[1]:
+        raise ValueError("levels must have F entries")
+    P = (1 if fit_intercept else 0) + q + int((lv - 1).sum())
+    K = _size(offsets) - 1
+    coef = thetas if beta is None else beta
+    if beta is not None and _size(coef) != P:
+        raise ValueError("beta must be [P]: one coefficient vector for every partition")
+    if thetas is not None and (_size(coef) != K * P or
+                               (len(_shape(coef)) == 2 and _shape(coef) != (K, P))):
+        raise ValueError("thetas must be [K, P]: one row per partition")
+    _check_rows(offsets, _shape(Xn)[0], y)
+    _center_scale(center, scale, q, "q (the numeric columns)")
+    dev = _require_gpu(device)
+    Xd, cd8, yd, offs, lv, cen, sca = _cat_inputs(Xn, codes, y, offsets, levels, center, scale,
+                                                  dev)
+    od, wd = _gof_extras(family, eta_offset, exposure, sample_weight, dev)
+    bd = _dev_f64(coef, dev).reshape(-1)
+    F = cd8.shape[1]
+    f64 = dict(dtype=torch.float64, device=dev)
+    gram, score = torch.empty((K, P, P), **f64), torch.empty((K, P), **f64)
+    gsum = torch.empty((P, P), **f64) if return_sum else None
+    ssum = torch.empty((P,), **f64) if return_sum else None
+    rc = _hip.load().dlsa_glm_gram_categorical(
+        fam, _GRAM_KINDS[kind], _ptr(Xd), _ptr(cd8), _ptr(yd), _ptr(od), _ptr(wd),
+        offs.ctypes.data_as(ctypes.c_void_p), K, q, F, lv.ctypes.data_as(ctypes.c_void_p),
+        int(bool(fit_intercept)), _ptr(cen), _ptr(sca), _ptr(bd),
+        P if thetas is not None else 0, int(rows_per_chunk), _ptr(gram), _ptr(score), _ptr(gsum),
+        _ptr(ssum), _stream(dev))
+    _hip.check(rc, "dlsa_glm_gram_categorical")
+    out = {"gram": gram, "score": score}
+    if return_sum:
+        out.update(gram_sum=gsum, score_sum=ssum)
+    return out
+
+
 _ROWS_STREAMS = ("eta", "mu", "dev_res", "pearson_res", "leverage")  # the C entry's order
 _ROWS_OUTPUTS = _ROWS_STREAMS + ("cooks",)
 

@@ -737,6 +737,39 @@ int dlsa_glm_gram_batched_chunked(int32_t family, int32_t kind, const double* X,
                                   void* stream);
 
 /*
+ * Score outer products on the categorical-code layout (Xn [n, q] fp64, codes
+ * [n, F] uint8, levels [F] on the host, as dlsa_logistic_fit_categorical
+ * takes them): dlsa_glm_gram_batched_chunked's semantics on the dummy-expanded
+ * design -- parameter order [intercept][q numeric][factor 0: levels 1..]...,
+ * gram [K, P, P] both triangles and exactly symmetric, score [K, P], an empty
+ * partition exact zeros, beta_part_stride 0 or P, gram_sum / score_sum NULL or
+ * the sums over k ascending -- at 8 q + F + 8 bytes per row (plus 8 per row
+ * extra), each streamed twice: a measuring sweep that sizes the fixed-point
+ * grids of the histograms from the terms themselves, then the categorical
+ * pass with the row weights (d_i, s_i) in place of the Newton pass's.
+ * Limits and errors are the categorical fit's: P <= DLSA_MAX_P_FUSED,
+ * intercept + q <= 16, F <= 16 and histograms that fit the LDS, else
+ * DLSA_E_UNSUPPORTED; an offset with the logistic family, a kind or a stride
+ * out of range DLSA_E_INVALID; a code >= levels[f] DLSA_E_INVALID, found by
+ * the sweep before the gram pass is launched (the outputs are then not
+ * written).  rows_per_chunk = 0: the categorical fit's chunk plan.
+ * Each dummy row or column entry is a fixed-point sum: within n_k R 2^-60 B
+ * of the fp64-exact sum in the worst case (n_k the partition's rows, R the
+ * rows of its largest chunk, at least 1024, B the partition's largest term
+ * of that entry's kind: |d|, |s| or |d x_j|); the numeric block is summed in
+ * fp64.  Two calls give the same bits.  A partition with a term that is not
+ * finite (a NaN weight, offset, y or x) gets an all-NaN gram and score; no
+ * other partition is touched.
+ */
+int dlsa_glm_gram_categorical(int32_t family, int32_t kind, const double* Xn,
+                              const uint8_t* codes, const double* y, const double* eta_offset,
+                              const double* row_weight, const int64_t* offsets, int32_t K,
+                              int32_t q, int32_t F, const int32_t* levels, int32_t fit_intercept,
+                              const double* center, const double* scale, const double* betas,
+                              int64_t beta_part_stride, int32_t rows_per_chunk, double* gram,
+                              double* score, double* gram_sum, double* score_sum, void* stream);
+
+/*
  * Row diagnostics: one more pass over the dense layout (8 (p + 1) bytes per
  * row plus 8 per row extra read, each once; 8 per requested output written)
  * that gives, per row i of partition k at its coefficient vector beta_k:
