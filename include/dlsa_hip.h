@@ -481,7 +481,13 @@ int dlsa_logistic_loglik_batched(const double* X, const double* y,
  * in which some dummy column has no rows gets DLSA_STATUS_MISSING_LEVEL and
  * all-zero outputs, the reference's "fake zero matrix".  Codes >= levels[f]
  * fail the call with DLSA_E_INVALID.  Limits: F <= 16, levels[f] in 1..256,
- * fit_intercept + q <= 16.  levels is a HOST array [F]; opt may be NULL
+ * fit_intercept + q <= 16.  Before any launch, F > 16 or a levels[f] outside
+ * 1..256 is DLSA_E_INVALID, and P > DLSA_MAX_P_FUSED, fit_intercept + q > 16
+ * or histograms that do not fit the LDS DLSA_E_UNSUPPORTED (no shape inside
+ * the limits overflows the LDS: with one replica per histogram the largest,
+ * 16 factors beside 13 numeric columns without an intercept, takes 153 240 of
+ * the 163 840 bytes).
+ * levels is a HOST array [F]; opt may be NULL
  * (hessian_mode is ignored: every pass is exact; warm_start runs a 1/16-prefix
  * level first only when the partitions average >= 2^19 rows).  Workspace:
  * there is no size query for this layout; opt->workspace is used when it is
@@ -748,8 +754,9 @@ int dlsa_glm_gram_batched_chunked(int32_t family, int32_t kind, const double* X,
  * grids of the histograms from the terms themselves, then the categorical
  * pass with the row weights (d_i, s_i) in place of the Newton pass's.
  * Limits and errors are the categorical fit's: P <= DLSA_MAX_P_FUSED,
- * intercept + q <= 16, F <= 16 and histograms that fit the LDS, else
- * DLSA_E_UNSUPPORTED; an offset with the logistic family, a kind or a stride
+ * intercept + q <= 16 and histograms that fit the LDS, else
+ * DLSA_E_UNSUPPORTED; F <= 16 and levels[f] in 1..256, else DLSA_E_INVALID;
+ * an offset with the logistic family, a kind or a stride
  * out of range DLSA_E_INVALID; a code >= levels[f] DLSA_E_INVALID, found by
  * the sweep before the gram pass is launched (the outputs are then not
  * written).  rows_per_chunk = 0: the categorical fit's chunk plan.
